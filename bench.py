@@ -7,7 +7,7 @@ Metric (BASELINE.json): batched FFTs/s + achieved HBM GB/s, N=1024 C2C forward, 
 already resident in HBM (config 2 of BASELINE.json).  With N GPUs every rank owns its own 4 GiB
 batch (config 5: weak scaling, no data-path collective; RCCL only reduces the timings).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `--gpus N` without a launcher (WORLD_SIZE unset) starts the N ranks itself: the parent process never touches
@@ -232,6 +232,32 @@ def device_info(torch, dev):
     return info
 
 
+DUMP_ROWS = 4096          # FFTs of the timed output written by --dump-outputs, over all ranks (4096 x 8 KiB = 32 MiB at N = 1024)
+
+
+def dump_outputs(sm, o_ptr, n, nffts, out_dir, rank, world):
+    """--dump-outputs DIR: what the timed path returned to its caller in its last step -- the (nFFTs, N) complex64 output of
+    SMFFT_DIT_external<FFT_1024_forward> -- as DIR/output.npy, float32 of shape (rows, N, 2) (re, im), next to DIR/output_rows.npy
+    (float64: which FFTs of the batch those rows are).  All of it when the batch has at most DUMP_ROWS / world FFTs, else a fixed
+    seeded sample of that many (same rows in every run).  In a multi-rank run rank r writes output_rank<r>.npy / output_rows_rank<r>.npy."""
+    import numpy as np
+
+    rows = max(1, DUMP_ROWS // world)
+    if nffts <= rows:
+        idx = np.arange(nffts)
+    else:
+        idx = np.sort(np.random.default_rng(20240 + rank).choice(nffts, rows, replace=False))
+    out = np.empty((len(idx), n, 2), np.float32)
+    row_bytes = n * 8
+    for k, i in enumerate(idx):
+        if sm.lib.smfft_memcpy_d2h(out[k].ctypes.data, o_ptr + int(i) * row_bytes, row_bytes) != 0:
+            raise SystemExit("--dump-outputs: smfft_memcpy_d2h failed")
+    suffix = f"_rank{rank}" if world > 1 else ""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, f"output{suffix}.npy"), out)
+    np.save(os.path.join(out_dir, f"output_rows{suffix}.npy"), idx.astype(np.float64))
+
+
 def _sig(x, digits=6):
     """floats to `digits` significant digits (the compact line is bounded), NaN / inf -> None (strict JSON)"""
     if isinstance(x, float):
@@ -393,9 +419,13 @@ def main():
     ap.add_argument("--no-configs", action="store_true", help="skip the config 3 / config 4 measurements (N = 1 extras)")
     ap.add_argument("--no-plain", action="store_true",
                     help="skip the plain-hipMalloc measurement (for rocprofv3 --stats runs: every launch of the roofline kernel is then on the same pair, so the profiler's average duration is comparable with roofline.kernel_ms)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the output of the last one (a fixed sample of at most 4096 FFTs) as DIR/*.npy")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ:
         if args.gpus > 1:
             raise SystemExit(spawn_ranks(args))
@@ -551,6 +581,8 @@ def main():
     # the plain pair first (so that the contract's timed region is the last thing before the reductions)
     plain_wall, plain_kernel_ms = run_timed(p_in.ptr, p_out.ptr, False) if p_in else (0.0, 0.0)
     wall, kernel_ms = run_timed(pa.value, pb.value, True)
+    if args.dump_outputs:
+        dump_outputs(sm, pb.value, n, nffts, args.dump_outputs, rank, world)    # before anything else writes pb
 
     # sanity on the timed output (cheap, outside the timed region): spot-check 4 FFTs of BOTH outputs against torch fp64
     want = torch.fft.fft(xs, dim=-1)

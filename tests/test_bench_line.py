@@ -111,3 +111,34 @@ def test_compact_line_of_round_6_with_eight_ranks_keeps_its_summary():
     assert s["convolution_ms"][0] <= 1.95, s["convolution_ms"]     # (the same item: the application on the reference's contract)
     assert min(s["config3_frac_2048_4096"]) >= 0.54
     assert len(line["per_rank"]["kernel_ms"]) == 8 and line["roofline_own_input"] is not None
+
+
+def test_dump_outputs_writes_a_fixed_sample_of_the_timed_output(tmp_path):
+    """--dump-outputs: the rows of the timed output buffer as float32 (rows, N, 2) next to their row numbers; the whole batch when it is
+    small, else the same seeded sample in every run, under 64 MB over all ranks.  The library's copy is replaced by memmove on host memory."""
+    import ctypes
+    import types
+
+    import numpy as np
+
+    def memcpy_d2h(dst, src, nbytes):
+        ctypes.memmove(dst, src, nbytes)
+        return 0
+    sm = types.SimpleNamespace(lib=types.SimpleNamespace(smfft_memcpy_d2h=memcpy_d2h))
+    n = 1024
+    rng = np.random.default_rng(5)
+    for nffts, world in ((37, 1), (3 * bench.DUMP_ROWS, 1), (3 * bench.DUMP_ROWS, 4)):
+        y = (rng.standard_normal((nffts, n)) + 1j * rng.standard_normal((nffts, n))).astype(np.complex64)
+        for rank in range(world):
+            for run in ("a", "b"):
+                bench.dump_outputs(sm, y.ctypes.data, n, nffts, str(tmp_path / f"{nffts}_{world}_{run}"), rank, world)
+            suffix = f"_rank{rank}" if world > 1 else ""
+            got = np.load(tmp_path / f"{nffts}_{world}_a" / f"output{suffix}.npy")
+            rows = np.load(tmp_path / f"{nffts}_{world}_a" / f"output_rows{suffix}.npy")
+            assert got.dtype == np.float32 and rows.dtype == np.float64 and got.shape == (len(rows), n, 2)
+            assert len(rows) == min(nffts, bench.DUMP_ROWS // world) and np.all(np.diff(rows) > 0) and rows[-1] < nffts
+            np.testing.assert_array_equal(got[..., 0] + 1j * got[..., 1], y[rows.astype(np.int64)])
+            for name in (f"output{suffix}.npy", f"output_rows{suffix}.npy"):
+                np.testing.assert_array_equal(np.load(tmp_path / f"{nffts}_{world}_a" / name), np.load(tmp_path / f"{nffts}_{world}_b" / name))
+        total = sum(f.stat().st_size for f in (tmp_path / f"{nffts}_{world}_a").iterdir())
+        assert total <= 64e6, total
