@@ -53,6 +53,14 @@ int smfft_ct_multiple_unfused_benchmark(const void* d_input, void* d_output, int
  * smfft_ct_multiple_benchmark. */
 int smfft_ct_multiple_percall_benchmark(const void* d_input, void* d_output, int FFT_size, int nFFTs, int inverse, int reorder, double* FFT_time);
 
+/* Decimation-in-frequency transform (no upstream twin): natural in -> bit-reversed out: d_output[f*N + j] = X_f[bitrev(j)]; the
+ * exact inverse partner of reorder == 0 (reorder == 0 of the other direction applied to this output gives N * d_input), so a
+ * circular convolution needs no reordering: IFFT_noreorder(DIF(x) .* DIF(h)) = N (x (*) h).  N = 32 .. 4096, un-normalised.
+ * The benchmark form as smfft_ct_external_benchmark (elapsed ms ADDED to *FFT_time; an unsupported length prints
+ * "Error wrong FFT length!" and launches nothing); the launch form as smfft_launch (0, a hipError_t, or -1 for an unsupported length). */
+int smfft_ct_dif_external_benchmark(const void* d_input, void* d_output, int FFT_size, int nFFTs, int inverse, double* FFT_time);
+int smfft_ct_dif_launch(const void* d_input, void* d_output, int FFT_size, int nFFTs, int inverse, void* hip_stream);
+
 /* ---- Stockham C2C family (un-normalised INVERSE transform, ST:76), N = 32 .. 4096 ------------
  * (upstream: 256 .. 4096; the smaller lengths are an extension) */
 /* FFT_external_benchmark / FFT_multiple_benchmark (ST:306-346, :348-384). */

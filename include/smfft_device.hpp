@@ -10,6 +10,9 @@
 //                                         (blockDim.x = fft_length / 4, contiguous data), the reference-shaped kernels
 //                                         SMFFT_DIT_external<P>(in, out) etc., and the same functions in the engine's
 //                                         tiled contract (namespace smfft::tiled)
+//   smfft/smfft_dif.hpp                   do_SMFFT_CT_DIF<P>, do_SMFFT_CT_DIF_registers<P>: the decimation-in-frequency transform of a
+//                                         no-reorder class (natural order in, bit-reversed spectrum out; the exact inverse partner
+//                                         of do_SMFFT_CT_DIT<FFT_<N>_*_noreorder>), same contract
 //   smfft/smfft_engine.hpp                smfft::Engine<N, DIR, REORDER>: registers in, registers out
 // Reference: SMFFT_CooleyTukey_C2C/FFT-GPU-32bit.cu:334-551, README.md:10-60.
 #pragma once
@@ -17,3 +20,4 @@
 #include "smfft/SM_FFT_stockham_parameters.hpp"
 #include "smfft/smfft_engine.hpp"
 #include "smfft/smfft_device_functions.hpp"
+#include "smfft/smfft_dif.hpp"

@@ -12,10 +12,12 @@ from .api import (  # noqa: F401
     LIB_PATH,
     NREUSES,
     c2c,
+    c2c_dif,
     c2r,
     host_transform,
     last_pair_info,
     launch,
+    launch_dif,
     lib,
     pinned_empty,
     r2c,

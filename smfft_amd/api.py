@@ -41,6 +41,8 @@ _SIGS = {
     "smfft_rc_external_benchmark": (_i, [_vp, _vp, _i, _i, _i, _dp]),
     "smfft_rc_multiple_benchmark": (_i, [_vp, _vp, _i, _i, _dp]),
     "smfft_launch": (_i, [_i, _i, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "smfft_ct_dif_external_benchmark": (_i, [_vp, _vp, _i, _i, _i, _dp]),
+    "smfft_ct_dif_launch": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "smfft_copy_launch": (_i, [_vp, _vp, ctypes.c_longlong, _vp]),
     "smfft_gpu_ct": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _dp, _dp]),
     "smfft_gpu_st": (_i, [_vp, _vp, _i, _i, _i, _dp, _dp]),
@@ -200,6 +202,14 @@ def launch(family, path, d_input, d_output, FFT_size, nFFTs, inverse=None, reord
         raise RuntimeError(f"smfft_launch({family},{path},N={FFT_size}) -> {rc}")
 
 
+def launch_dif(d_in, d_out, N, nFFTs, inverse=False, stream=0):
+    """Decimation-in-frequency transform, launch only (no events, no sync): d_out[f*N + j] = X_f[bitrev(j)] -- natural order in,
+    bit-reversed spectrum out, the exact inverse partner of the no-reorder transforms (smfft_ct_dif_launch)."""
+    rc = lib.smfft_ct_dif_launch(d_in, d_out, N, nFFTs, int(inverse), stream)
+    if rc != 0:
+        raise RuntimeError(f"smfft_ct_dif_launch(N={N}) -> {rc}")
+
+
 # ---- NumPy-level conveniences used by the tests (host arrays in/out, still the HIP path) -----------
 def _run(x, out_dtype, out_shape, fn):
     din = DeviceBuffer.from_host(x)
@@ -222,6 +232,18 @@ def c2c(x, inverse=False, reorder=True, path="external"):
         return _run(x, np.complex64, x.shape, fn)
     f = FFT_external_benchmark if path == "external" else FFT_multiple_benchmark
     return _run(x, np.complex64, x.shape, lambda i, o: f(i, o, n, nffts, inverse, reorder, "ct"))
+
+
+def c2c_dif(x, inverse=False):
+    """x: (nFFTs, N) complex64 host array -> the DIF transform through the HIP library: out[f, j] = X_f[bitrev(j)], X the
+    un-normalised DFT of row f (inverse: the + sign).  c2c(c2c_dif(x), inverse=True, reorder=False) = N * x."""
+    x = np.ascontiguousarray(x, dtype=np.complex64)
+    nffts, n = x.shape
+
+    def fn(i, o):
+        t = ctypes.c_double(0.0)
+        return lib.smfft_ct_dif_external_benchmark(i, o, n, nffts, int(inverse), ctypes.byref(t)), t.value
+    return _run(x, np.complex64, x.shape, fn)
 
 
 def stockham_c2c(x, inverse=True):

@@ -113,6 +113,20 @@ int dispatch_st(const float2* in, float2* out, int N, int count, int path, hipSt
         default:   return -1;
     }
 }
+// the DIF transform (natural order in, bit-reversed spectrum out): its own entry points, no reorder / family value of its own
+int dispatch_dif(const float2* in, float2* out, int N, int count, int inverse, hipStream_t st) {
+    switch (N) {
+        case 32:   return smfft::launch_dif<32>(in, out, count, inverse, st);
+        case 64:   return smfft::launch_dif<64>(in, out, count, inverse, st);
+        case 128:  return smfft::launch_dif<128>(in, out, count, inverse, st);
+        case 256:  return smfft::launch_dif<256>(in, out, count, inverse, st);
+        case 512:  return smfft::launch_dif<512>(in, out, count, inverse, st);
+        case 1024: return smfft::launch_dif<1024>(in, out, count, inverse, st);
+        case 2048: return smfft::launch_dif<2048>(in, out, count, inverse, st);
+        case 4096: return smfft::launch_dif<4096>(in, out, count, inverse, st);
+        default:   return -1;
+    }
+}
 // FFT_size is the REAL length; the kernels are instantiated on the complex length L = FFT_size/2 (RC:404-428)
 int dispatch_rc(const float2* in, float2* out, int FFT_size, int count, int inverse, int path, hipStream_t st) {
     const smfft::LaunchOptions opt = cur_options(pacing_for(out, rc_pacing(FFT_size / 2).ordinary, rc_pacing(FFT_size / 2).mixed));
@@ -397,6 +411,15 @@ int smfft_launch(int family, int path, const void* d_input, void* d_output, int 
     }
     if (family == 2) return dispatch_rc(in, out, FFT_size, path ? nFFTs / SMFFT_NREUSES : nFFTs, inverse != 0, path, st);
     return -1;
+}
+
+int smfft_ct_dif_external_benchmark(const void* d_input, void* d_output, int FFT_size, int nFFTs, int inverse, double* FFT_time) {
+    return timed([&] { return dispatch_dif((const float2*)d_input, (float2*)d_output, FFT_size, nFFTs, inverse != 0, 0); }, FFT_time);
+}
+
+int smfft_ct_dif_launch(const void* d_input, void* d_output, int FFT_size, int nFFTs, int inverse, void* hip_stream) {
+    read_env();
+    return dispatch_dif((const float2*)d_input, (float2*)d_output, FFT_size, nFFTs, inverse != 0, (hipStream_t)hip_stream);
 }
 
 int smfft_copy_launch(const void* d_input, void* d_output, long long n_float2, void* hip_stream) {

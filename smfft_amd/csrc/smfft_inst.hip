@@ -184,6 +184,16 @@ int launch_ct<SMFFT_N>(const float2* d_input, float2* d_output, int count, int i
     return launch_ct_multiple<SMFFT_N>(d_input, d_output, count, inverse, reorder, path, opt, stream);
 }
 
+template <>
+int launch_dif<SMFFT_N>(const float2* d_input, float2* d_output, int count, int inverse, hipStream_t stream) {
+    if (count <= 0) return 0;
+    constexpr int per_block = dif_external_ffts_per_block<CT_CLASS(_forward_noreorder)>();
+    const dim3 grid((unsigned)((count + per_block - 1) / per_block)), block(SMFFT_N <= 1024 ? 256 : SMFFT_N / 4);
+    if (!inverse) SMFFT_DIF_external<CT_CLASS(_forward_noreorder)><<<grid, block, 0, stream>>>(d_input, d_output, count);
+    else          SMFFT_DIF_external<CT_CLASS(_inverse_noreorder)><<<grid, block, 0, stream>>>(d_input, d_output, count);
+    return (int)hipGetLastError();
+}
+
 #if SMFFT_N == 1024
 int launch_stream_copy(const float2* d_input, float2* d_output, long n_float2, int grid_cap, int pace, hipStream_t stream) {
     long ntiles = n_float2 / 4096;

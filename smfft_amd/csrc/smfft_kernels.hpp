@@ -4,6 +4,7 @@
 //   SMFFT_DIT_multiple<P>             CT/FFT-GPU-32bit.cu:553-572   NREUSES FFTs in LDS per load/store
 //   FFT_GPU_external/multiple<P>      ST/FFT-GPU-32bit-Stockham.cu:243-278
 //   FFT_GPU_R2C_C2R_external/multiple<P,D>  RC/FFT-GPU-32bit-Stockham.cu:349-384
+//   SMFFT_DIF_external<P>             (no upstream twin) natural order in, bit-reversed spectrum out: smfft_dif.hpp
 //
 // The EXTERNAL kernels use 256-thread workgroups that own a tile of 4096 float2 (= 4096/N FFTs) and
 // P::fft_sm_required = 4352 float2 of LDS (34 KiB -> 4 workgroups = 16 waves per CU), on the float2 engine
@@ -20,6 +21,7 @@
 #include <type_traits>
 
 #include "smfft/smfft_device_functions.hpp"
+#include "smfft/smfft_dif.hpp"
 #include "smfft/smfft_planar.hpp"
 
 namespace smfft {
@@ -909,6 +911,40 @@ SMFFT_DIT_external_occ3(const float2* d_input, float2* d_output, int nFFTs, int 
     __shared__ float2 s_input[const_params::tile_sm_required];
     smfft::c2c_external_body<const_params::fft_size, const_params::fft_direction, const_params::fft_reorder>(d_input, d_output, nFFTs, pace, s_input);
 }
+
+// DIF (decimation in frequency, include/smfft/smfft_dif.hpp): d_output[f N + j] = X_f[bitrev(j)] for f < nFFTs, the exact inverse partner
+// of the no-reorder transforms.  Blocks of 256 threads hold 1024 / N transforms up to N = 1024, N / 4 threads one transform above;
+// a thread loads elements t + m N/4 (each wave instruction 512 contiguous bytes), runs the DIF ladder on its registers with the
+// block's LDS as the image, and stores the positions 4 t + m it ends with: a wave's four stores cover 2 KiB contiguous, no
+// permutation through LDS.  LDS: 4 x the block's threads float2 (N = 4096: 32 KiB).
+template <class const_params>
+__global__ void __launch_bounds__(const_params::fft_size <= 1024 ? 256 : const_params::fft_size / 4)
+SMFFT_DIF_external(const float2* __restrict__ d_input, float2* __restrict__ d_output, int nFFTs) {
+    static_assert(const_params::fft_reorder == 0, "the DIF transform belongs to the no-reorder classes");
+    constexpr int N = const_params::fft_size, Q = N / 4;
+    constexpr int kThreads = N <= 1024 ? 256 : Q, kPerBlock = 4 * kThreads / N;
+    __shared__ float2 s_image[4 * kThreads];
+    const int f = threadIdx.x / Q, t = threadIdx.x % Q;
+    const long fft = (long)blockIdx.x * kPerBlock + f;
+    const bool live = fft < nFFTs;                       // (the last block of a batch that is not a multiple of kPerBlock)
+    const float2* in = d_input + fft * N;
+    float2* out = d_output + fft * N;
+    float2 x[4];
+    if (live) {
+#pragma unroll
+        for (int m = 0; m < 4; ++m) x[m] = smfft::gload(in + t + m * Q);
+    } else {
+#pragma unroll
+        for (int m = 0; m < 4; ++m) x[m] = make_float2(0.f, 0.f);
+    }
+    smfft::dif_ladder<N, const_params::fft_direction, Q, true, true>(x, s_image, t, f * N);
+    if (live) {
+#pragma unroll
+        for (int m = 0; m < 4; ++m) smfft::gstore(out + 4 * t + m, x[m]);
+    }
+}
+template <class const_params>
+constexpr int dif_external_ffts_per_block() { return const_params::fft_size <= 1024 ? 1024 / const_params::fft_size : 1; }
 
 // Launch bounds of the compact (in-LDS) kernels: every one is compiled for FOUR waves per SIMD -- what the schedule is built on
 // (the rotation of the wave priorities has four ranks; five waves per SIMD at 96 registers measured 3-27 % slower:

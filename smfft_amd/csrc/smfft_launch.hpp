@@ -37,6 +37,10 @@ int launch_st(const float2* d_input, float2* d_output, int count, int path, cons
 template <int L>
 int launch_rc(const float2* d_input, float2* d_output, int count, int inverse, int path, const LaunchOptions& opt, hipStream_t stream);
 
+// DIF transform (SMFFT_DIF_external): natural order in, bit-reversed spectrum out, N = 32..4096; count = number of FFTs.
+template <int N>
+int launch_dif(const float2* d_input, float2* d_output, int count, int inverse, hipStream_t stream);
+
 // calibration copy of n_float2 elements (multiple of 4096) with the external kernels' access shape
 int launch_stream_copy(const float2* d_input, float2* d_output, long n_float2, int grid_cap, int pace, hipStream_t stream);
 // the same access shape, writes only / reads only

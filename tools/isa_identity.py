@@ -1,0 +1,95 @@
+#!/usr/bin/env python3
+"""Do the kernels of a base commit compile to the same gfx950 code on the working tree?  (CPU only: hipcc cross-compiles.)
+
+Compiles, on a checkout of BASE (git archive into a temporary directory) and on the working tree, with the Makefile's flags:
+  smfft_amd/csrc/smfft_inst.hip   both objects (SMFFT_INST_PART = 1, 2 with tools/inst_flags.py) of all 8 lengths
+  examples/*.hip                  the files BASE has
+to device assembly (hipcc -S --cuda-device-only) and compares every kernel BASE has, text of its body and its .amdhsa descriptor,
+with the basic-block labels (.LBB<f>_<n>) and the function-local symbols renumbered in order of appearance.
+    python tools/isa_identity.py [BASE=HEAD]        exit status 0: every kernel identical"""
+import os
+import re
+import subprocess
+import sys
+import tempfile
+from concurrent.futures import ThreadPoolExecutor
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+from inst_flags import part_flags  # noqa: E402
+
+HIPCC = "/opt/rocm/bin/hipcc"
+FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-fno-slp-vectorize", "-Wall", "-Wno-unused-function"]
+SIZES = (32, 64, 128, 256, 512, 1024, 2048, 4096)
+
+
+def units(tree):
+    out = []
+    for n in SIZES:
+        for part in (1, 2):
+            out.append((f"smfft_inst_{n}_part{part}", "smfft_amd/csrc/smfft_inst.hip", part_flags(n, part) + [f"-DSMFFT_N={n}"]))
+    for ex in sorted(os.listdir(os.path.join(tree, "examples"))):
+        if ex.endswith(".hip"):
+            out.append((ex, "examples/" + ex, []))
+    return out
+
+
+def compile_unit(tree, rel, extra, dst):
+    cmd = [HIPCC] + FLAGS + ["-I" + os.path.join(tree, "include")] + extra + ["-S", "--cuda-device-only", os.path.join(tree, rel), "-o", dst]
+    p = subprocess.run(cmd, capture_output=True, text=True)
+    if p.returncode != 0:
+        raise RuntimeError(p.stderr[-3000:])
+    return open(dst).read()
+
+
+def kernels(asm):
+    """{mangled name: normalised text of the function body + its kernel descriptor}"""
+    out = {}
+    for m in re.finditer(r"^(_Z\w+):\s*(?:;[^\n]*)?\n(.*?)^\.Lfunc_end\d+:", asm, re.S | re.M):
+        name, body = m.group(1), m.group(2)
+        d = re.search(r"\.amdhsa_kernel %s\n(.*?)\.end_amdhsa_kernel" % re.escape(name), asm, re.S)
+        out[name] = normalise(body + (d.group(1) if d else ""))
+    return out
+
+
+def normalise(text):
+    seen = {}
+
+    def label(m):
+        return seen.setdefault(m.group(0), f".L{len(seen)}")
+    text = re.sub(r"\.LBB\d+_\d+|\.Ltmp\d+|\.Lfunc_begin\d+|\.Lfunc_end\d+", label, text)
+    lines = (re.sub(r"\s*;.*$", "", l).rstrip() for l in text.split("\n"))       # comments (they name blocks by number too)
+    return "\n".join(l for l in lines if l.strip())
+
+
+def main():
+    base = sys.argv[1] if len(sys.argv) > 1 else "HEAD"
+    with tempfile.TemporaryDirectory() as tmp:
+        base_tree = os.path.join(tmp, "base")
+        os.makedirs(base_tree)
+        archive = subprocess.run(["git", "-C", ROOT, "archive", base], capture_output=True, check=True).stdout
+        subprocess.run(["tar", "-x", "-C", base_tree], input=archive, check=True)
+        jobs = []
+        for tag, tree in (("base", base_tree), ("tree", ROOT)):
+            for name, rel, extra in units(base_tree):
+                jobs.append((tag, name, tree, rel, extra, os.path.join(tmp, f"{tag}_{name}.s")))
+        with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as ex:
+            asm = dict(zip([(j[0], j[1]) for j in jobs], ex.map(lambda j: compile_unit(*j[2:]), jobs)))
+    total, differ = 0, []
+    for name in sorted({j[1] for j in jobs}):
+        a, b = kernels(asm[("base", name)]), kernels(asm[("tree", name)])
+        for k, text in a.items():
+            total += 1
+            if b.get(k) != text:
+                differ.append((name, k, "missing" if k not in b else "differs"))
+        added = sorted(set(b) - set(a))
+        print(f"{name:32s} {len(a):4d} kernels of {base}: {len(a) - sum(1 for d in differ if d[0] == name):4d} identical"
+              + (f"; {len(added)} new" if added else ""))
+    for name, k, why in differ:
+        print(f"  {why}: {name} {k}")
+    print(f"{total} kernels of {base} compared, {len(differ)} differ")
+    return 1 if differ else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
