@@ -94,6 +94,31 @@ int smfft_launch(int family, int path, const void* d_input, void* d_output, int 
  * the external kernels' global access shape and grid, no FFT: the same-run copy ceiling. */
 int smfft_copy_launch(const void* d_input, void* d_output, long long n_float2, void* hip_stream);
 
+/* ---- FIR filter banks (overlap-save; no upstream counterpart) ----------------------------------
+ * Linear filtering of C long complex signals by a bank of K filters of M taps, in one kernel from segment load to filtered output.
+ * Signal d_signal: C channels x L float2, channel c at element c*L (L = signal_length, any value >= 1, 64-bit).  Taps d_taps:
+ * K x M float2, filter k at element k*M, 1 <= M <= FFT_size - 1.  Output d_output: C*K*L float2,
+ *   y[(c*K + k)*L + n], n < L:
+ *   correlate == 0 (convolve):  y = sum_{m<M} h_k[m] x_c[n - m], x_c[i < 0] = 0      = np.convolve(x_c, h_k)[:L]
+ *   correlate != 0 (correlate): y = sum_{m<M} conj(h_k[m]) x_c[n + m], x_c[i >= L] = 0 = np.correlate(np.r_[x_c, zeros(M-1)], h_k, 'valid')
+ *                               (the matched filter; NumPy conjugates its second argument)
+ * FFT_size N = 256 .. 4096: each channel is cut into S = ceil(L / V) segments of N samples, V = N - M + 1 new outputs each; a segment is
+ * transformed once for all K filters.
+ * Spectra d_spectra: K x N float2, the prepared form of the taps, public so that a caller may produce it any other way:
+ *   H_k[j] = DFT_N(pad_N(g_k))[j] / N, natural order, un-normalised forward sign (exp(-2 pi i jm/N)),
+ *   g_k = h_k (convolve), g_k[m] = conj(h_k[M-1-m]) (correlate).
+ * The spectra depend on the mode, so prepare and launch must be called with the same `correlate`.
+ * smfft_fir_prepare writes d_spectra from d_taps (no workspace); smfft_fir_launch filters.  Both only enqueue on hip_stream (no
+ * synchronisation).  The benchmark form is smfft_fir_launch on the null stream timed with events, elapsed ms ADDED to *FFT_time,
+ * synchronous (as smfft_ct_dif_external_benchmark).  Return values as smfft_launch: 0, a hipError_t, or -1 for an unsupported
+ * combination (N not in 256 .. 4096, n_taps < 1 or >= N, a count <= 0, signal_length < 0), found before any HIP call;
+ * signal_length == 0 launches nothing and returns 0. */
+int smfft_fir_prepare(const void* d_taps, int n_taps, int n_filters, int FFT_size, int correlate, void* d_spectra, void* hip_stream);
+int smfft_fir_launch(const void* d_signal, long long signal_length, int n_channels, const void* d_spectra, int n_filters, int n_taps,
+                     int FFT_size, int correlate, void* d_output, void* hip_stream);
+int smfft_fir_benchmark(const void* d_signal, long long signal_length, int n_channels, const void* d_spectra, int n_filters, int n_taps,
+                        int FFT_size, int correlate, void* d_output, double* FFT_time);
+
 /* ---- L3 wrappers: host buffers in, host buffers out (alloc, H2D, nRuns launches, D2H, free) ---- */
 /* GPU_smFFT_4elements (CT:827-908). */
 int smfft_gpu_ct(const void* h_input, void* h_output, int FFT_size, int nFFTs, int inverse, int reorder,

@@ -14,6 +14,10 @@ from .api import (  # noqa: F401
     c2c,
     c2c_dif,
     c2r,
+    fir,
+    fir_fft_size,
+    fir_launch,
+    fir_prepare,
     host_transform,
     last_pair_info,
     launch,
