@@ -1,6 +1,6 @@
 """The overlap-save FIR filter banks on an MI355X (smfft_fir_prepare / smfft_fir_launch, smfft_amd.fir*) against fp64 NumPy: both modes at
-every transform length over a grid of taps, channels, filters and signal lengths; the filter-group split; the prepared spectra; a
-caller's stream; 64-bit output offsets.
+every transform length over a grid of taps, channels, filters and signal lengths; the filter-group split, uneven groups included; the
+grid-stride loop past the grid cap; the prepared spectra; a caller's stream; 64-bit output offsets.
 
 Tolerances per (channel, filter) row: relL2 <= 1e-6 and max|err| / max|ref| <= 5e-6 -- two fp32 transforms and a product, at the
 library's per-FFT bounds (5e-7 / 1e-6, oracle/np_reference.py) each.  The rounding error of an FFT convolution is spread over the
@@ -255,3 +255,125 @@ def test_output_offsets_beyond_two_to_the_31(sm):
                 _check_rows(got[None, None], want[None, None], f"{mode} k={k} n0={n0}", seg[None], hk[None])
     for b in (dx, dh, dspec, dout):
         b.free()
+
+
+# ---- the grid-stride loop and the filter groups ------------------------------------------------------------------------------
+GRID_CAP = 12288               # smfft_fir.hip kFirGridCap: workgroups along the segment tiles; more tiles are grid-strided
+GROUP_TARGET = 2048            # smfft_fir.hip kFirTargetWorkgroups: the filter-group rule's target
+
+
+def _tiles(L, C, N, M):
+    return -(-fm.Window(L, N, M, False).segments() * C // (4096 // N))
+
+
+def _group_plan(tiles, K):
+    """(group size, grid rows) of a launch: the rule of smfft_fir.hpp fir_filter_group_size, restated"""
+    groups = max(1, min(K, -(-GROUP_TARGET // tiles)))
+    size = -(-K // groups)
+    return size, -(-K // size)
+
+
+@pytest.mark.parametrize("N", SIZES)
+@pytest.mark.parametrize("mode", MODES)
+def test_grid_stride_loop_with_wrapped_prefetch(sm, N, mode):
+    """M = N - 1 (V = 2 outputs per segment), C = 3, K = 3: about 2.5 x 12288 tiles, so every workgroup runs two or three tiles and
+    after its last filter prefetches the first filter's spectrum for its next tile.  S = 10240 F + 1 segments per channel (F = 4096 / N
+    per tile): tiles straddle channel boundaries for N < 4096 and the last one is partial; L = 2 S - 1 leaves the last segment one
+    output.  Every row against fp64."""
+    M, C, K = N - 1, 3, 3
+    F = 4096 // N
+    S = 10240 * F + 1
+    L = 2 * S - 1
+    tiles = _tiles(L, C, N, M)
+    assert 2 * GRID_CAP < tiles < 3 * GRID_CAP and _group_plan(tiles, K) == (3, 1)
+    assert F == 1 or (S % F and C * S % F)
+    rng = np.random.default_rng(12288 + N + (mode == "correlate"))
+    x, h = _rand(rng, (C, L)), _rand(rng, (K, M))
+    got = _run(sm, x, h, N, mode)
+    _check_rows(got, _reference(x, h, mode == "correlate"), f"grid-stride N={N} {mode}", x, h)
+
+
+def _sampled_windows(sm, dout, x, h, L, starts, mode, what, W):
+    C, K = x.shape[0], h.shape[0]
+    M = h.shape[1]
+    for c in range(C):
+        for k in range(K):
+            hk = h[k].astype(np.complex128)
+            for n0 in starts[c]:
+                got = np.empty(W, np.complex64)
+                assert sm.lib.smfft_memcpy_d2h(got.ctypes.data, dout.ptr + ((c * K + k) * L + n0) * 8, W * 8) == 0
+                if mode == "correlate":
+                    seg = np.r_[x[c, n0:n0 + W + M - 1].astype(np.complex128), np.zeros(max(0, n0 + W + M - 1 - L))]
+                    want = np.correlate(seg, hk, "valid")
+                else:
+                    lo = max(0, n0 - (M - 1))
+                    seg = x[c, lo:n0 + W].astype(np.complex128)
+                    want = np.convolve(seg, hk)[n0 - lo:n0 - lo + W]
+                _check_rows(got[None, None], want[None, None], f"{what} c={c} k={k} n0={n0}", seg[None], hk[None])
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_grid_stride_loop_at_a_realistic_shape(sm, mode):
+    """N = 1024, M = 257, C = 3 channels of L = 16e6 samples, K = 2: 15,626 tiles, past the grid cap.  Sampled windows against
+    np.convolve / np.correlate: the first and last of every (channel, filter) row (their segments' tiles straddle two channels), one in
+    the middle, and the one where the grid-stride loop's second pass starts (tile 12288)."""
+    N, M, C, K, L = 1024, 257, 3, 2, 16_000_000
+    V, F = N - M + 1, 4096 // N
+    S = -(-L // V)
+    tiles = _tiles(L, C, N, M)
+    assert tiles > GRID_CAP and S % F and _group_plan(tiles, K) == (2, 1)
+    rng = np.random.default_rng(16)
+    x = rng.standard_normal((C, 2 * L), dtype=np.float32).view(np.complex64)
+    h = _rand(rng, (K, M))
+    W = 3000
+    starts = [[0, L // 2 + 11, L - W] for _ in range(C)]
+    c2, s2 = divmod(GRID_CAP * F, S)                  # the first segment of tile 12288
+    starts[c2].append(max(0, s2 * V - W // 2))
+    dx, dh = sm.DeviceBuffer.from_host(x), sm.DeviceBuffer.from_host(h)
+    dspec, dout = sm.DeviceBuffer(K * N * 8), sm.DeviceBuffer((C * K * L + GUARD) * 8)
+    try:
+        assert sm.lib.smfft_memset(dout.ptr + C * K * L * 8, 0x5A, GUARD * 8) == 0
+        sm.fir_prepare(dh.ptr, dspec.ptr, M, K, N, mode)
+        sm.fir_launch(dx.ptr, L, C, dspec.ptr, K, M, N, dout.ptr, mode)
+        assert sm.lib.smfft_synchronize() == 0
+        guard = np.empty(GUARD * 8, np.uint8)
+        assert sm.lib.smfft_memcpy_d2h(guard.ctypes.data, dout.ptr + C * K * L * 8, GUARD * 8) == 0
+        assert np.all(guard == 0x5A), "the kernel wrote past its output"
+        _sampled_windows(sm, dout, x, h, L, starts, mode, f"L=16e6 {mode}", W)
+    finally:
+        for b in (dx, dh, dspec, dout):
+            b.free()
+
+
+@pytest.mark.parametrize("N,L,K,plan", [
+    (4096, 2 * 700 - 1, 7, (3, 3)),      # 3 groups of 3 filters asked and launched; the last holds one
+    (4096, 2 * 450 - 1, 12, (3, 4)),     # 5 groups asked, group size 3: 4 grid rows
+    (256, 2 * (699 * 16 + 5) - 1, 7, (3, 3)),
+    (256, 2 * (449 * 16 + 7) - 1, 12, (3, 4)),
+])
+@pytest.mark.parametrize("mode", MODES)
+def test_uneven_filter_groups(sm, N, L, K, plan, mode):
+    """M = N - 1 on 700 / 450 tiles: filter groups of the rule's size with a shorter last group, and a grid of fewer rows than the
+    groups the rule asked for.  Every row equals the K = 1 launch of its filter (the same spectrum) to the bit and is within bounds
+    against fp64."""
+    M = N - 1
+    tiles = _tiles(L, 1, N, M)
+    assert tiles == (700 if K == 7 else 450) and _group_plan(tiles, K) == plan
+    asked = min(K, -(-GROUP_TARGET // tiles))
+    if K == 7:
+        assert asked == plan[1] and K - (plan[1] - 1) * plan[0] == 1       # the last group holds one filter
+    else:
+        assert asked == 5 and plan[1] == 4                                 # fewer grid rows than groups asked for
+    rng = np.random.default_rng(N + K + (mode == "correlate"))
+    x, h = _rand(rng, (1, L)), _rand(rng, (K, M))
+    dh, dspec = sm.DeviceBuffer.from_host(h), sm.DeviceBuffer(K * N * 8)
+    sm.fir_prepare(dh.ptr, dspec.ptr, M, K, N, mode)
+    assert sm.lib.smfft_synchronize() == 0
+    spectra = dspec.to_host(np.complex64, (K, N))
+    dh.free()
+    dspec.free()
+    got = _run(sm, x, h, N, mode, spectra=spectra)
+    for k in range(K):
+        one = _run(sm, x, h[k:k + 1], N, mode, spectra=spectra[k:k + 1])
+        assert np.array_equal(one[0, 0].view(np.uint32), got[0, k].view(np.uint32)), (N, K, mode, k)
+    _check_rows(got, _reference(x, h, mode == "correlate"), f"groups N={N} K={K} {mode}", x, h)
