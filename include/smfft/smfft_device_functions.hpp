@@ -50,6 +50,7 @@ namespace smfft {
 // ------------------------------------------------------------------------------------------------
 template <int L, int DIR>
 __device__ __forceinline__ void hermitian_pass(float2* sf, int u) {
+    static_assert(L <= 2048, "R2C / C2R: complex length L = real length / 2 <= 2048 (the twiddle step 4096 / (2L) of the split / merge)");
     constexpr int T = L / 16;
     constexpr float ohx = DIR ? -0.5f : 0.5f;   // upstream's (ohx, ohy) = (1/2, -1/2) forward, (-1/2, 1/2) inverse (RC:289-328)
     if (DIR) {
@@ -605,7 +606,11 @@ __device__ __forceinline__ void quarter_fft(float2 (&x)[4], float2* s, int t, in
         else quarter_small_noreorder<N, DIR>(s, t, region_offset);
         return;
     }
-    if constexpr ((ENGINE == 2 || (ENGINE == 0 && quarter_lanes_default(N))) && N <= 256 && !OUT_REGS && !kOneWaveNatural && !(kPhases && N == 256 && !REORDER && BLOCK_THREADS <= 64)) {   // the ladder on lanes and registers (QuarterLanes above)
+    // (not for a transform of 8 lanes alone in its block -- the Stockham programs' N = 32: the exchange of lane bit 2 reads its partner
+    //  through a rotation of the 16-lane row, half of whose lanes no thread of such a block runs, and a DPP read from an inactive lane
+    //  leaves the destination unwritten; that block takes the LDS form below)
+    constexpr bool kRowOfLanes = BLOCK_THREADS >= 16 || N > 32;
+    if constexpr ((ENGINE == 2 || (ENGINE == 0 && quarter_lanes_default(N))) && N <= 256 && !OUT_REGS && !kOneWaveNatural && !(kPhases && N == 256 && !REORDER && BLOCK_THREADS <= 64) && kRowOfLanes) {   // the ladder on lanes and registers (QuarterLanes above)
         QuarterLanes<N, DIR, REORDER>::template lds_to_lds<IN_REGS>(x, s, t, region_offset);
         return;
     }
@@ -886,6 +891,7 @@ template <int L, int DIR>
 struct HermitianTwiddles { float2 w[2]; };
 template <int L, int DIR>
 __device__ __forceinline__ HermitianTwiddles<L, DIR> hermitian_twiddles_quarter(int t) {
+    static_assert(L <= 2048, "R2C / C2R: complex length L = real length / 2 <= 2048 (the twiddle step 4096 / (2L) of the split / merge)");
     constexpr float ohx = DIR ? -0.5f : 0.5f;
     HermitianTwiddles<L, DIR> h;
 #pragma unroll

@@ -868,8 +868,9 @@ def test_device_function_in_a_runtime_loop(sm, oracle_lib, n, wave64):
 
 @pytest.mark.parametrize("n", [256, 512, 1024, 2048, 4096])
 def test_reference_shaped_stockham_kernel(sm, oracle_lib, n):
-    """FFT_GPU_external<FFT_N><<<nFFTs, N/4, N*8>>>(in, out) calling do_FFT_Stockham_mk6 on exactly N float2 of dynamic
-    LDS (ST:243-258, 309-319): the + sign transform, natural order."""
+    """FFT_GPU_external<FFT_N><<<nFFTs, N/4, N*8>>>(in, out) on exactly N float2 of dynamic LDS (ST:243-258, 309-319): the + sign
+    transform, natural order.  In the default build the kernel hands the block's registers to do_FFT_Stockham_C2C_registers_out, not
+    to do_FFT_Stockham_mk6; tests/test_device_contract_gpu.py runs do_FFT_Stockham_mk6 itself."""
     import ctypes
     ex = _examples(sm)
     fn = ex.smfft_example_reference_shape_st
