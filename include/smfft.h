@@ -11,8 +11,8 @@
  *
  * Conventions shared with the reference:
  *   - complex data is interleaved float (re, im) = float2; FFT f of a batch is at element f*N;
- *   - d_* pointers are DEVICE pointers owned by the caller; transforms are out of place and leave
- *     the input untouched; all transforms are un-normalised;
+ *   - d_* pointers are DEVICE pointers owned by the caller; transforms leave the input untouched (unless
+ *     d_output == d_input, see "Buffer contract" below); all transforms are un-normalised;
  *   - the *_benchmark calls time exactly one kernel launch with events and ADD the milliseconds to
  *     *FFT_time (CT:598,660-662); they are synchronous;
  *   - return value 0 = ok.  Unsupported lengths print "Error wrong FFT length!" and return 0 with
@@ -33,6 +33,7 @@ extern "C" {
 void smfft_init(void);
 
 /* ---- Cooley-Tukey C2C family, N = 32 .. 4096 ------------------------------------------------ */
+/* (alignment, footprint and in-place use of every *_benchmark call's buffers: "Buffer contract" below, at smfft_launch) */
 /* FFT_external_benchmark (CT:583-664): d_output[f] = FFT(d_input[f]), f < nFFTs.
  * reorder != 0: natural-order DFT; reorder == 0: DFT of the bit-reversed-index input (the DIT
  * butterfly network applied to natural-order data), exactly as fft_reorder = 0 upstream. */
@@ -56,6 +57,7 @@ int smfft_ct_multiple_percall_benchmark(const void* d_input, void* d_output, int
 /* Decimation-in-frequency transform (no upstream twin): natural in -> bit-reversed out: d_output[f*N + j] = X_f[bitrev(j)]; the
  * exact inverse partner of reorder == 0 (reorder == 0 of the other direction applied to this output gives N * d_input), so a
  * circular convolution needs no reordering: IFFT_noreorder(DIF(x) .* DIF(h)) = N (x (*) h).  N = 32 .. 4096, un-normalised.
+ * Buffers (alignment, footprint, in place): "Buffer contract" at smfft_launch.
  * The benchmark form as smfft_ct_external_benchmark (elapsed ms ADDED to *FFT_time; an unsupported length prints
  * "Error wrong FFT length!" and launches nothing); the launch form as smfft_launch (0, a hipError_t, or -1 for an unsupported length). */
 int smfft_ct_dif_external_benchmark(const void* d_input, void* d_output, int FFT_size, int nFFTs, int inverse, double* FFT_time);
@@ -81,6 +83,18 @@ int smfft_rc_external_benchmark(const float* d_input, float* d_output, int FFT_s
 /* FFT_multiple_benchmark (RC:435-467), forward only as upstream. */
 int smfft_rc_multiple_benchmark(const float* d_input, float* d_output, int FFT_size, int nFFTs, double* FFT_time);
 
+/* ---- Buffer contract of the transforms (smfft_launch, the *_benchmark calls, DIF, FIR, smfft_host_transform; tests/test_buffers_gpu.py)
+ * Alignment: every buffer pointer must be 8-byte aligned -- for the real arrays of R2C / C2R, an even number of floats from an
+ *   8-byte-aligned base.  Nothing else is required: interior pointers of any allocation are valid, smfft_malloc_pair buffers included.
+ * Footprint: a call reads only input FFTs [0, count) and writes only output FFTs [0, count); count = nFFTs for path 0 and DIF, the
+ *   slot count for paths 1 and 2 (CT: smfft_ct_multiple_benchmark's nFFTs/100 rule, N = 32 / 64 in groups of 4 / 2; ST and RC:
+ *   nFFTs/100).  FIR: smfft_fir_prepare reads taps[0, K*M) and writes spectra[0, K*N); smfft_fir_launch / _benchmark read
+ *   signal[0, C*L) and spectra[0, K*N) and write out[0, C*K*L).  Nothing before the first element or after the last is touched.
+ * Aliasing: d_output == d_input is allowed for every smfft_launch family and path (and so for the *_benchmark calls, which launch
+ *   the same kernels), for DIF, and for smfft_host_transform (h_output == h_input); partial overlap never is.  FIR's signal, spectra
+ *   and output must not overlap.
+ * A transform's result does not depend on where its buffers are. */
+
 /* ---- launch-only forms (no events, no synchronisation) on a caller-provided hipStream_t --------
  * family: 0 = CT, 1 = ST, 2 = RC.  path: 0 = external, 1 = multiple.  For family 2, FFT_size is
  * the REAL length.  family 1 (the Stockham program, + sign only upstream, ST:76): inverse != 0 is the
@@ -88,7 +102,7 @@ int smfft_rc_multiple_benchmark(const float* d_input, float* d_output, int FFT_s
  * bench.py and smfft_host_transform; same kernels as the *_benchmark calls (capturable into a hipGraph by the caller).
  * Returns 0, a hipError_t, or -1 for an unsupported (family, FFT_size). */
 int smfft_launch(int family, int path, const void* d_input, void* d_output, int FFT_size, int nFFTs,
-                 int inverse, int reorder, void* hip_stream);
+                 int inverse, int reorder, void* hip_stream);   /* buffers: "Buffer contract" above */
 
 /* Calibration: streams n_float2 elements (a multiple of 4096) from d_input to d_output with exactly
  * the external kernels' global access shape and grid, no FFT: the same-run copy ceiling. */
@@ -103,7 +117,7 @@ int smfft_copy_launch(const void* d_input, void* d_output, long long n_float2, v
  *   correlate != 0 (correlate): y = sum_{m<M} conj(h_k[m]) x_c[n + m], x_c[i >= L] = 0 = np.correlate(np.r_[x_c, zeros(M-1)], h_k, 'valid')
  *                               (the matched filter; NumPy conjugates its second argument)
  * FFT_size N = 256 .. 4096: each channel is cut into S = ceil(L / V) segments of N samples, V = N - M + 1 new outputs each; a segment is
- * transformed once for all K filters.
+ * transformed once for all K filters.  Alignment, footprints and overlap: "Buffer contract" (at smfft_launch).
  * Spectra d_spectra: K x N float2, the prepared form of the taps, public so that a caller may produce it any other way:
  *   H_k[j] = DFT_N(pad_N(g_k))[j] / N, natural order, un-normalised forward sign (exp(-2 pi i jm/N)),
  *   g_k = h_k (convolve), g_k[m] = conj(h_k[M-1-m]) (correlate).
@@ -141,7 +155,7 @@ int smfft_gpu_c2r(float* h_output, const void* h_input, int FFT_size, int nFFTs,
  * writes them directly over PCIe, both directions at once (config-2 batch: 88 ms = 97 GB/s in + out against
  * 118 ms through the slabs; SMFFT_HOST_ZERO_COPY=0 keeps the slab pipeline, slab_ffts / lanes then apply).  family / FFT_size / inverse / reorder as for smfft_launch (family 2: real length; input and
  * output are FFT_size * 4 bytes per FFT either way).  *elapsed_ms = wall-clock time of the whole call
- * (end to end, PCIe included); the first call also builds the cached pipeline (smfft_host_pipeline_release
+ * (end to end, PCIe included; buffers: "Buffer contract" at smfft_launch); the first call also builds the cached pipeline (smfft_host_pipeline_release
  * frees it).  Returns 0, -1 for an unsupported (family, FFT_size), -4 when the pipeline cannot be allocated,
  * or a hipError_t. */
 int smfft_host_transform(int family, const void* h_input, void* h_output, int FFT_size, long long nFFTs,

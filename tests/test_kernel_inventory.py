@@ -1,7 +1,7 @@
-"""Every kernel libsmfft_amd.so ships is in tests/kernel_inventory.py with a GPU test that compares it with fp64 (or a reason why it
-is not a transform), and every test the inventory names exists.  CPU only: the kernels are enumerated from the built library's
-host-side kernel handles -- one data symbol per __global__ instantiation, whose demangled name is the kernel's -- so nothing is
-recompiled."""
+"""Every kernel libsmfft_amd.so ships is in tests/kernel_inventory.py with a GPU test that compares it with fp64 and one that runs
+it on guarded buffers (or a reason why it is not a transform), and every test the inventory names exists.  CPU only: the kernels are
+enumerated from the built library's host-side kernel handles -- one data symbol per __global__ instantiation, whose demangled name is
+the kernel's -- so nothing is recompiled."""
 import ast
 import os
 import re
@@ -64,9 +64,10 @@ def test_every_shipped_kernel_is_in_the_inventory(shipped):
 
 def test_every_transform_names_a_call_and_an_fp64_test():
     for name, entry in inv.KERNELS.items():
-        assert set(entry) == {"call", "tests"}, name
+        assert set(entry) == {"call", "tests", "bounds"}, name
         assert entry["call"].startswith("smfft_"), name
         assert entry["tests"], f"{name}: no GPU test compares it with fp64"
+        assert entry["bounds"], f"{name}: no GPU test runs it on guarded buffers (tests/test_buffers_gpu.py)"
     for name, reason in inv.NOT_TRANSFORMS.items():
         assert reason.strip(), name
 
@@ -80,10 +81,10 @@ def _gpu_tests(path):
     return names, gpu
 
 
-def test_named_tests_exist_and_are_gpu_tests():
+def _named_tests_exist_and_are_gpu_tests(key):
     files = {}
     for name, entry in inv.KERNELS.items():
-        for tid in entry["tests"]:
+        for tid in entry[key]:
             m = re.fullmatch(r"(tests/test_\w+\.py)::(test_\w+)", tid)
             assert m, f"{name}: malformed test id {tid!r}"
             path = os.path.join(ROOT, m.group(1))
@@ -93,3 +94,11 @@ def test_named_tests_exist_and_are_gpu_tests():
             names, gpu = files[path]
             assert m.group(2) in names, f"{name}: {tid} does not exist"
             assert gpu, f"{name}: {m.group(1)} is not a GPU test module"
+
+
+def test_named_tests_exist_and_are_gpu_tests():
+    _named_tests_exist_and_are_gpu_tests("tests")
+
+
+def test_bounds_tests_exist_and_are_gpu_tests():
+    _named_tests_exist_and_are_gpu_tests("bounds")
