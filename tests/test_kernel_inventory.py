@@ -1,5 +1,5 @@
 """Every kernel libsmfft_amd.so ships is in tests/kernel_inventory.py with a GPU test that compares it with fp64 and one that runs
-it on guarded buffers (or a reason why it is not a transform), and every test the inventory names exists.  CPU only: the kernels are
+it on guarded buffers and one that probes it per element and in isolation (or a reason why it is not a transform), and every test the inventory names exists.  CPU only: the kernels are
 enumerated from the built library's host-side kernel handles -- one data symbol per __global__ instantiation, whose demangled name is
 the kernel's -- so nothing is recompiled."""
 import ast
@@ -64,10 +64,11 @@ def test_every_shipped_kernel_is_in_the_inventory(shipped):
 
 def test_every_transform_names_a_call_and_an_fp64_test():
     for name, entry in inv.KERNELS.items():
-        assert set(entry) == {"call", "tests", "bounds"}, name
+        assert set(entry) == {"call", "tests", "bounds", "probes"}, name
         assert entry["call"].startswith("smfft_"), name
         assert entry["tests"], f"{name}: no GPU test compares it with fp64"
         assert entry["bounds"], f"{name}: no GPU test runs it on guarded buffers (tests/test_buffers_gpu.py)"
+        assert entry["probes"], f"{name}: no GPU test probes it per element and in isolation (tests/test_probes_gpu.py)"
     for name, reason in inv.NOT_TRANSFORMS.items():
         assert reason.strip(), name
 
@@ -102,3 +103,7 @@ def test_named_tests_exist_and_are_gpu_tests():
 
 def test_bounds_tests_exist_and_are_gpu_tests():
     _named_tests_exist_and_are_gpu_tests("bounds")
+
+
+def test_probes_tests_exist_and_are_gpu_tests():
+    _named_tests_exist_and_are_gpu_tests("probes")
