@@ -1,12 +1,17 @@
 """Every __global__ kernel that libsmfft_large.so ships (N = 8192 / 16384 single-pass C2C, include/smfft_large.h), with the public call
 that reaches it and the GPU tests that compare it with fp64, run it on guarded buffers and probe it per element and in isolation
-(tests/test_large_cpu.py checks this list against the built library's kernels, with the rule of tests/test_kernel_inventory.py).
+(the `large` cases of tests/test_probes_gpu.py among them).  tests/test_large_cpu.py checks this list against the built library's
+kernels, with the rule of tests/test_kernel_inventory.py.
 Names are the demangled kernel names without their parameter lists."""
 
 LARGE = "tests/test_large_gpu.py::"
-_TESTS = [LARGE + "test_large_parity", LARGE + "test_large_round_trip"]
-_BOUNDS = [LARGE + "test_large_guarded_buffers_and_interior_pointers", LARGE + "test_large_in_place"]
-_PROBES = [LARGE + "test_large_dft_matrix_probe", LARGE + "test_large_zero_mean_accuracy", LARGE + "test_large_isolation_and_exact_scaling"]
+PROBE_SUITE = "tests/test_probes_gpu.py::"
+_TESTS = [LARGE + "test_large_parity", LARGE + "test_large_round_trip", LARGE + "test_large_concurrent_streams_and_co_residency"]
+_BOUNDS = [LARGE + "test_large_guarded_buffers_and_interior_pointers", LARGE + "test_large_in_place",
+           LARGE + "test_large_guarded_batches_and_offsets", LARGE + "test_large_64bit_offsets_8192"]
+_PROBES = [LARGE + "test_large_dft_matrix_probe", LARGE + "test_large_zero_mean_accuracy", LARGE + "test_large_isolation_and_exact_scaling",
+           LARGE + "test_large_position_invariance",
+           PROBE_SUITE + "test_dft_matrix_probe", PROBE_SUITE + "test_zero_mean_accuracy", PROBE_SUITE + "test_isolation_and_exact_scaling"]
 
 KERNELS = {
     f"smfft::large::large_c2c<{n}, {d}>": {

@@ -10,12 +10,15 @@ A case id is "<kind>-N<n>-<fwd|inv>[-noreorder]-k<k>"; kinds:
   st_external          FFT_GPU_external (inverse: the Stockham program; forward: the extension on the CT kernels)
   st_multiple          FFT_GPU_multiple (inverse) and the forward extension on SMFFT_DIT_multiple
   r2c_* / c2r_*        FFT_GPU_R2C_C2R_external / _multiple, N reals <-> N / 2 packed complex
-  dif                  SMFFT_DIF_external: natural order in, bit-reversed spectrum out"""
+  dif                  SMFFT_DIF_external: natural order in, bit-reversed spectrum out
+  large                large_c2c of libsmfft_large.so (smfft_amd.large.c2c): N = 8192 and 16384, natural order, k = 1, a persistent
+                       grid of G = smfft_amd.large.grid(N) workgroups over the batch"""
 import math
 from collections import namedtuple
 
 C2C_SIZES = [32, 64, 128, 256, 512, 1024, 2048, 4096]
 R2C_SIZES = [512, 1024, 2048, 4096]
+LARGE_SIZES = [8192, 16384]
 # the kernels path 2 has of its own (everything else on path 2 is the path-1 kernel): (N, reorder)
 PERCALL_KERNELS = [(n, 1) for n in C2C_SIZES] + [(32, 0), (64, 0)]
 
@@ -65,6 +68,8 @@ def _cases():
     for n in R2C_SIZES:
         out += [Case("r2c_external", n, 0, 1, 1), Case("c2r_external", n, 1, 1, 1)]
         out += [Case("r2c_multiple", n, 0, 1, k) for k in (1, 2)] + [Case("c2r_multiple", n, 1, 1, k) for k in (1, 2)]
+    for n in LARGE_SIZES:
+        out += [Case("large", n, inv, 1, 1) for inv in (0, 1)]
     return out
 
 

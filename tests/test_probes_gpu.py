@@ -14,6 +14,9 @@ A1  DFT-matrix probes (test_dft_matrix_probe).  The batch is the N x N identity 
     second application maps the first one's error through a DFT, whose gain on the largest element is the same N as its gain on
     max |ref_row|: k applications add k ceilings.  Higher radices fold the same roundings into fewer operations, so the radix-2
     chain bounds them.
+    The `large` kind (N = 8192, 16384) runs the identity in chunks of 2^23 elements (the whole of it would take ~12 GiB of host
+    memory at 16384) and takes the expected output of impulse j, exactly W_N^{-+(j m mod N)} at output m, from one fp64 table
+    indexed by the integer product: the same ceiling and rms, every |ref| = 1.
 A2  Zero-mean accuracy (test_zero_mean_accuracy): one fixed-seed complex (R2C: real) Gaussian batch of >= 2^21 values, aggregate
     relL2 ||Y - Y64||_F / ||Y64||_F <= 5e-7 sqrt(k), the library's per-FFT bound.
 A3  Ratchet: tests/accuracy_ratchet.json holds, per case id, the figures A1 and A2 measured on an MI355X (tools/accuracy_ratchet.py
@@ -26,6 +29,11 @@ B   Isolation and exact scaling (test_isolation_and_exact_scaling): a clean Gaus
     are row 0, a row inside the first workgroup's tile, the first and the last row of the ragged last tile, the last transform and, on
     the `multiple` paths, the rows on both sides of every chain the balanced schedule cuts.  The `multiple` paths run k = 1, 2, 3 under
     the plain schedule and under smfft_set_multiple_balance(2) and (7).
+    The `large` kernels are persistent: G = smfft_amd.large.grid(N) workgroups, workgroup w transforms rows w, w + G, w + 2G, ...
+    in turn and carries its registers and LDS image from one to the next.  Their batch is 3G + G/2 rows (3 or 4 rounds, the last
+    one ragged), poisoned in every round -- row 0, row G - 1, the first and the last row of the ragged round among them -- with row
+    f + G clean after several poisoned rows f, so that what a workgroup carries into its next FFT reaches a finite row.  Their
+    exponents differ between rows f and f + 1 and between rows f and f + G, so a leak between them cannot scale exactly.
     FIR filter banks (test_fir_*): every channel scaled by 2^e scales its outputs exactly; a complex NaN at one sample turns exactly
     the stored windows of the segments that load it (tools/fir_plan_model.py) into NaN for every filter and leaves every other
     word alone; a NaN tap makes exactly its filter's spectrum row and output rows NaN."""
@@ -48,6 +56,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RATCHET = os.path.join(ROOT, "tests", "accuracy_ratchet.json")
 NREUSES = 100                  # the `multiple` paths transform the first nFFTs / 100 slots
 SCALES = (-40, -13, 0, 11, 40)
+LARGE_SCALES = (-40, 11, -13, 40)   # the `large` kind's, chosen by the parities of the row and of its round
 BALANCES = (0, 2, 7)           # 0: one chain per workgroup; g >= 2: a persistent grid of g workgroups
 
 
@@ -123,6 +132,9 @@ def _transform(sm, case, x, k=None, balance=0):
         return sm.r2c(x)
     if case.kind == "c2r_external":
         return sm.c2r(x)
+    if case.kind == "large":
+        from smfft_amd import large
+        return large.c2c(x, bool(case.inv))
     raise AssertionError(case)
 
 
@@ -174,9 +186,33 @@ def gauss_batch(case):
     return (rng.standard_normal((2 ** 21 // w, w)) + 1j * rng.standard_normal((2 ** 21 // w, w))).astype(np.complex64)
 
 
+LARGE_PROBE_CHUNK = 1 << 23    # elements of the identity per call of the `large` kind's probe
+
+
+def _large_probe_errors(sm, case):
+    """A1 of the `large` kind: the N x N identity in chunks of impulses.  Output m of impulse j is W_N^{-+(j m mod N)}, read from one
+    fp64 table at the integer product; every |ref| is 1 (to fp64 rounding), so max |ref_row| = 1 and |err| is the relative error."""
+    n = case.n
+    table = np.exp((1 if case.inv else -1) * 2j * np.pi * np.arange(n) / n)
+    m = np.arange(n, dtype=np.int64)
+    worst, sq = 0.0, 0.0
+    step = max(1, LARGE_PROBE_CHUNK // n)
+    for j0 in range(0, n, step):
+        j = np.arange(j0, min(n, j0 + step), dtype=np.int64)
+        x = np.zeros((len(j), n), np.complex64)
+        x[np.arange(len(j)), j] = 1
+        got = _transform(sm, case, x)
+        err = np.abs(got - table[(j[:, None] * m) & (n - 1)]).ravel()
+        worst = max(worst, float(err.max()))
+        sq += float(np.dot(err, err))
+    return worst, float(np.sqrt(sq / (n * n)))
+
+
 def probe_errors(sm, case):
     """(largest, rms) of the per-element errors |err| / max |ref_row| of the DFT-matrix probe (at k = 1 the rms is the batch's relL2:
     every |ref| is 1 there)"""
+    if case.kind == "large":
+        return _large_probe_errors(sm, case)
     x = probe_batch(case)
     got = _transform(sm, case, x)
     want = _reference(case, x)
@@ -226,8 +262,25 @@ def _cut_chains(ntiles, reuses, g):
     return [(b // reuses, b % reuses) for b in range(per_wg, total, per_wg) if b % reuses]
 
 
+def _large_iso_rows(n):
+    """(G, rows of the batch, the rows to poison) of the `large` kind: 3G + G/2 rows.  Poisoned in round 0: 0, G/3, G - 1; round 1:
+    G + G/2 + 1, 2G - 2; round 2: 2G + 5, 2G + G/2 + 3 (its workgroup's last FFT); the ragged round 3: its first row 3G and the last
+    row.  Rows f + G are clean after f = 0, G/3, G - 1, G + G/2 + 1 and 2G + 5."""
+    from smfft_amd import large
+    g = large.grid(n)
+    assert g >= 16, g
+    rows = 3 * g + g // 2
+    carried = (0, g // 3, g - 1, g + g // 2 + 1, 2 * g + 5)
+    poison = set(carried) | {2 * g - 2, 2 * g + g // 2 + 3, 3 * g, rows - 1}
+    for f in carried:
+        assert f + g < rows and f + g not in poison, (g, f)
+    return g, rows, sorted(poison)
+
+
 def _iso_rows(case):
     """(rows of the batch, the rows to poison): 23 tiles, the last one half full"""
+    if case.kind == "large":
+        return _large_iso_rows(case.n)[1:]
     nc = case.n // 2 if case.kind[:3] in ("r2c", "c2r") else case.n
     tile = max(1, 1024 // nc) if case.multiple else 4096 // nc      # Geometry<N>: kCompactFfts / kFftsPerBlock
     ntiles = 23
@@ -265,6 +318,10 @@ def test_isolation_and_exact_scaling(sm, case):
     else:
         x = (rng.standard_normal((rows, w)) + 1j * rng.standard_normal((rows, w))).astype(np.complex64)
     e = np.array([SCALES[r % len(SCALES)] for r in range(rows)])
+    if case.kind == "large":
+        g = _large_iso_rows(case.n)[0]
+        e = np.array([LARGE_SCALES[(r & 1) | ((r // g) & 1) << 1] for r in range(rows)])
+        assert (e[1:] != e[:-1]).all() and (e[g:] != e[:-g]).all(), "rows f, f + 1 and f + G need different exponents"
     y = np.ldexp(x.view(np.float32).reshape(rows, -1), e[:, None]).view(x.dtype)
     assert np.array_equal(np.ldexp(y.view(np.float32).reshape(rows, -1), -e[:, None]), x.view(np.float32).reshape(rows, -1))
     kinds = {}
