@@ -1,7 +1,7 @@
 // device_contract.hip -- test kernels for the header-only device API (include/smfft_device.hpp) that the library's own kernels do
 // not reach: user kernels written the way upstream's users write them (blockDim.x = fft_length / 4, the reference's grid arithmetic),
 // around do_FFT_Stockham_mk6 / _C2C / _R2C_C2R, the registers forms, the two-argument kernels of N = 32 ... 128, chains with a runtime
-// count, the smfft::tiled functions and -- in the -DNREUSES=3 build -- the header's `multiple` kernels.  tests/test_device_contract_gpu.py
+// count, the smfft::tiled functions (do_SMFFT_CT_DIT among them) and -- in the -DNREUSES=3 build -- the header's `multiple` kernels.  tests/test_device_contract_gpu.py
 // compares every one of them with fp64.  Built by smfft_amd/csrc/Makefile (libsmfft_device_contract*.so), never shipped.
 //
 // LDS canaries: a launcher given a non-null `canary` counter allocates the function's documented footprint plus kCanary float2, fills
@@ -105,13 +105,13 @@ __global__ void registers_kernel(const float2* d_input, float2* d_output, int* c
 
 // ------------------------------------------------------------------------------------------------
 // the tiled contract: 256 threads, 4096 / N transforms per workgroup at a stride of smfft::Geometry<N>::SF = 17 N / 16, in an LDS
-// array of 4352 float2.  FN as st_fill_call_drain.
+// array of 4352 float2.  FN as st_fill_call_drain; 5: smfft::tiled::do_SMFFT_CT_DIT<P> (P a CT class, N = P::fft_size).
 // ------------------------------------------------------------------------------------------------
-template <class P, int FN>
+template <class P, int FN, int N = P::fft_length>
 __global__ void tiled_kernel(const float2* d_input, float2* d_output, int* canary) {
     extern __shared__ float2 s_dynamic[];
     float2* s = s_dynamic;
-    constexpr int N = P::fft_length, SF = smfft::Geometry<N>::SF, footprint = 4352;
+    constexpr int SF = smfft::Geometry<N>::SF, footprint = 4352;
     const size_t block = (size_t)blockIdx.x * 4096;
     for (int i = threadIdx.x; i < 4096; i += 256) s[(i / N) * SF + i % N] = d_input[block + i];
     canary_fill(s, footprint, canary);
@@ -120,7 +120,8 @@ __global__ void tiled_kernel(const float2* d_input, float2* d_output, int* canar
     else if constexpr (FN == 1) smfft::tiled::do_FFT_Stockham_C2C<P, FFT_forward>(s);
     else if constexpr (FN == 2) smfft::tiled::do_FFT_Stockham_C2C<P, FFT_inverse>(s);
     else if constexpr (FN == 3) smfft::tiled::do_FFT_Stockham_R2C_C2R<P, FFT_forward>(s);
-    else smfft::tiled::do_FFT_Stockham_R2C_C2R<P, FFT_inverse>(s);
+    else if constexpr (FN == 4) smfft::tiled::do_FFT_Stockham_R2C_C2R<P, FFT_inverse>(s);
+    else smfft::tiled::do_SMFFT_CT_DIT<P>(s);
     __syncthreads();
     for (int i = threadIdx.x; i < 4096; i += 256) d_output[block + i] = s[(i / N) * SF + i % N];
     canary_check(s, footprint, canary);
@@ -167,6 +168,14 @@ int launch_tiled(int fn, const float2* in, float2* out, int nFFTs, int* canary, 
         case 4: if constexpr (P::fft_length <= 2048) { tiled_kernel<P, 4><<<grid, block, lds, st>>>(in, out, canary); break; } else return -1;
         default: return -1;
     }
+    return (int)hipGetLastError();
+}
+
+template <class P>
+int launch_tiled_ct(const float2* in, float2* out, int nFFTs, int* canary, hipStream_t st) {
+    constexpr int N = P::fft_size;
+    if (nFFTs % (4096 / N)) return -1;
+    tiled_kernel<P, 5, N><<<dim3(nFFTs / (4096 / N)), dim3(256), lds_bytes(4352, canary), st>>>(in, out, canary);
     return (int)hipGetLastError();
 }
 
@@ -218,6 +227,21 @@ extern "C" int dc_tiled(int fn, const void* in, void* out, int N, int nFFTs, int
     float2* o = (float2*)out;
     hipStream_t st = (hipStream_t)stream;
 #define X(n) case n: return launch_tiled<FFT_##n>(fn, i, o, nFFTs, canary, st);
+    switch (N) { DC_ST_SIZES(X) default: return -1; }
+#undef X
+}
+
+// smfft::tiled::do_SMFFT_CT_DIT<FFT_<N>_{forward,inverse}{,_noreorder}>, N = 32 ... 4096; nFFTs a multiple of 4096 / N
+extern "C" int dc_tiled_ct(int inverse, int reorder, const void* in, void* out, int N, int nFFTs, int* canary, void* stream) {
+    const float2* i = (const float2*)in;
+    float2* o = (float2*)out;
+    hipStream_t st = (hipStream_t)stream;
+#define X(n)                                                                                                   \
+    case n:                                                                                                    \
+        if (!inverse && reorder) return launch_tiled_ct<FFT_##n##_forward>(i, o, nFFTs, canary, st);          \
+        if (!inverse) return launch_tiled_ct<FFT_##n##_forward_noreorder>(i, o, nFFTs, canary, st);           \
+        if (reorder) return launch_tiled_ct<FFT_##n##_inverse>(i, o, nFFTs, canary, st);                      \
+        return launch_tiled_ct<FFT_##n##_inverse_noreorder>(i, o, nFFTs, canary, st);
     switch (N) { DC_ST_SIZES(X) default: return -1; }
 #undef X
 }

@@ -30,6 +30,7 @@ _ARGTYPES = {
     "dc_stockham": [_I, _VP, _VP, _I, _I, _VP, _VP],
     "dc_chain": [_I, _VP, _VP, _I, _I, _I, _VP],
     "dc_tiled": [_I, _VP, _VP, _I, _I, _VP, _VP],
+    "dc_tiled_ct": [_I, _I, _VP, _VP, _I, _I, _VP, _VP],
     "dc_stockham_registers": [_I, _I, _VP, _VP, _I, _I, _VP, _VP],
     "dc_ct_registers": [_I, _I, _VP, _VP, _I, _I, _VP, _VP],
     "dc_fft_gpu_external": [_VP, _VP, _I, _I, _VP],
@@ -208,6 +209,20 @@ def test_tiled_stockham_and_r2c(sm, n, fn, build):
     x = _complex(np.random.default_rng(700 * n + fn), (nffts, n))
     _check_both_footprints(sm, fn, lambda i, o, c: lib.dc_tiled(fn, i, o, n, nffts, c, None), x, _want(fn, n, x),
                            f"tiled {ST_FNS[fn]} N={n} build={build!r}")
+
+
+@pytest.mark.parametrize("build", BUILDS)
+@pytest.mark.parametrize("inv,reo", [(0, 1), (1, 1), (0, 0), (1, 0)])
+@pytest.mark.parametrize("n", SIZES)
+def test_tiled_ct_dit(sm, n, inv, reo, build):
+    """smfft::tiled::do_SMFFT_CT_DIT<FFT_<N>_{forward,inverse}{,_noreorder}>, all 32 classes: the tiled layout of
+    test_tiled_stockham_and_r2c (256 threads, 4096 / N transforms per workgroup at a stride of 17N/16, 4352 float2), the transform of
+    the class's direction and order (S1 / S2)."""
+    lib = _lib(sm, build)
+    nffts = BLOCKS * (4096 // n)
+    x = _complex(np.random.default_rng(750 * n + 10 * inv + reo), (nffts, n))
+    _check_both_footprints(sm, 1, lambda i, o, c: lib.dc_tiled_ct(inv, reo, i, o, n, nffts, c, None), x,
+                           ref.ct_c2c(x, bool(inv), bool(reo)), f"tiled CT N={n} inv={inv} reorder={reo} build={build!r}")
 
 
 # ------------------------------------------------------------------ full occupancy

@@ -1,9 +1,11 @@
 """Every public function of the header-only device API is in tests/device_function_inventory.py with GPU tests that compare it with
-fp64, and every test the inventory names exists and is a GPU test.  CPU only: the functions are read from the header text."""
+fp64 and GPU tests that probe it per element and in isolation (run by some case of tests/probe_cases.py HEADER_CASES), and every
+test the inventory names exists and is a GPU test.  CPU only: the functions are read from the header text."""
 import os
 import re
 
 from tests import device_function_inventory as inv
+from tests import probe_cases as pc
 from tests.test_kernel_inventory import _gpu_tests
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -73,15 +75,28 @@ def test_every_public_device_function_is_in_the_inventory():
 
 def test_every_entry_names_classes_and_fp64_tests():
     for name, entry in inv.FUNCTIONS.items():
-        assert set(entry) == {"classes", "tests"}, name
+        assert set(entry) == {"classes", "tests", "probes"}, name
         assert entry["classes"].strip(), name
         assert entry["tests"], f"{name}: no GPU test compares it with fp64"
+        assert entry["probes"], f"{name}: no GPU test probes it per element and in isolation (tests/test_device_probes_gpu.py)"
 
 
-def test_named_tests_exist_and_are_gpu_tests():
+def test_every_function_has_probe_cases():
+    """each function is run by a case of HEADER_CASES (through an entry point of probe_cases.HEADER_FUNCS that names it), and every
+    name there is an inventory function"""
+    run = {}
+    for c in pc.HEADER_CASES:
+        for name in pc.HEADER_FUNCS[c.func][1]:
+            run.setdefault(name, set()).add(c.id)
+    assert set(run) <= set(inv.FUNCTIONS), sorted(set(run) - set(inv.FUNCTIONS))
+    missing = sorted(set(inv.FUNCTIONS) - set(run))
+    assert not missing, f"inventory functions that no probe case runs: {missing}"
+
+
+def _named_tests_exist_and_are_gpu_tests(key):
     files = {}
     for name, entry in inv.FUNCTIONS.items():
-        for tid in entry["tests"]:
+        for tid in entry[key]:
             m = re.fullmatch(r"(tests/test_\w+\.py)::(test_\w+)", tid)
             assert m, f"{name}: malformed test id {tid!r}"
             path = os.path.join(ROOT, m.group(1))
@@ -91,3 +106,11 @@ def test_named_tests_exist_and_are_gpu_tests():
             names, gpu = files[path]
             assert m.group(2) in names, f"{name}: {tid} does not exist"
             assert gpu, f"{name}: {m.group(1)} is not a GPU test module"
+
+
+def test_named_tests_exist_and_are_gpu_tests():
+    _named_tests_exist_and_are_gpu_tests("tests")
+
+
+def test_probes_tests_exist_and_are_gpu_tests():
+    _named_tests_exist_and_are_gpu_tests("probes")

@@ -322,40 +322,55 @@ def test_isolation_and_exact_scaling(sm, case):
         g = _large_iso_rows(case.n)[0]
         e = np.array([LARGE_SCALES[(r & 1) | ((r // g) & 1) << 1] for r in range(rows)])
         assert (e[1:] != e[:-1]).all() and (e[g:] != e[:-g]).all(), "rows f, f + 1 and f + G need different exponents"
-    y = np.ldexp(x.view(np.float32).reshape(rows, -1), e[:, None]).view(x.dtype)
-    assert np.array_equal(np.ldexp(y.view(np.float32).reshape(rows, -1), -e[:, None]), x.view(np.float32).reshape(rows, -1))
-    kinds = {}
-    for i, r in enumerate(poison):
-        p = (0, w - 1, w // 2 + 1, (17 * r + 5) % w)[i % 4]      # the ends of a row among them (row 0 has its poison at 0)
-        kind = ("nan", "inf", "neginf_imag")[i % 3]
-        kinds[r] = kind
-        if case.real_in:
-            y[r, p] = {"nan": np.nan, "inf": np.inf, "neginf_imag": -np.inf}[kind]
-        else:
-            y[r, p] = {"nan": complex(np.nan, np.nan), "inf": complex(np.inf, y[r, p].imag),
-                       "neginf_imag": complex(y[r, p].real, -np.inf)}[kind]
-    clean_mask = np.ones(rows, bool)
-    clean_mask[poison] = False
+    y, kinds = poisoned_batch(x, e, poison, case.real_in)
     runs = [(k, g) for k in (1, 2, 3) for g in BALANCES] if case.multiple else [(1, 0)]
     for k, g in runs:
         what = f"{case.id[:-3]} k={k} balance={g}"
         clean = _transform(sm, case, x, k, g)
         dirty = _transform(sm, case, y, k, g)
-        cf = clean.view(np.float32).reshape(rows, -1)
-        df = dirty.view(np.float32).reshape(rows, -1)
-        assert np.isfinite(cf).all(), f"{what}: the clean batch gave non-finite outputs"
-        want = np.ldexp(cf, e[:, None]).view(np.uint32)
-        bad = np.nonzero((want[clean_mask] != df[clean_mask].view(np.uint32)).any(axis=1))[0]
-        assert bad.size == 0, f"{what}: unpoisoned rows {np.nonzero(clean_mask)[0][bad][:8].tolist()} are not 2^e x their clean rows"
-        for r in poison:
-            if case.real_out:
-                assert _non_finite(dirty[r]).all(), f"{what}: row {r} ({kinds[r]}) has finite outputs"
-                continue
-            nf_re, nf_im = _non_finite(dirty[r].real), _non_finite(dirty[r].imag)
-            if kinds[r] == "nan" and not case.real_in:
-                assert (nf_re & nf_im).all(), f"{what}: row {r} (complex NaN) has an output with a finite component"
-            else:
-                assert (nf_re | nf_im).all(), f"{what}: row {r} ({kinds[r]}) has a finite output"
+        assert_isolated_and_exact(clean, dirty, e, kinds, case.real_in, case.real_out, what)
+
+
+def poisoned_batch(x, e, poison, real_in):
+    """(y, kinds): row r of x scaled by 2^e[r], then a complex NaN, a +Inf real part or a -Inf imaginary part (kinds[r]) at one
+    position of each row in `poison` (the ends of a row among them; row 0 has its poison at 0)"""
+    rows, w = x.shape
+    y = np.ldexp(x.view(np.float32).reshape(rows, -1), e[:, None]).view(x.dtype)
+    assert np.array_equal(np.ldexp(y.view(np.float32).reshape(rows, -1), -e[:, None]), x.view(np.float32).reshape(rows, -1))
+    kinds = {}
+    for i, r in enumerate(poison):
+        p = (0, w - 1, w // 2 + 1, (17 * r + 5) % w)[i % 4]
+        kind = ("nan", "inf", "neginf_imag")[i % 3]
+        kinds[r] = kind
+        if real_in:
+            y[r, p] = {"nan": np.nan, "inf": np.inf, "neginf_imag": -np.inf}[kind]
+        else:
+            y[r, p] = {"nan": complex(np.nan, np.nan), "inf": complex(np.inf, y[r, p].imag),
+                       "neginf_imag": complex(y[r, p].real, -np.inf)}[kind]
+    return y, kinds
+
+
+def assert_isolated_and_exact(clean, dirty, e, kinds, real_in, real_out, what):
+    """every unpoisoned row of `dirty` is ldexp(its `clean` row, e) to the bit; every element of a poisoned row has a non-finite
+    component (both, for a complex NaN into a complex transform; C2R: every real)"""
+    rows = clean.shape[0]
+    clean_mask = np.ones(rows, bool)
+    clean_mask[list(kinds)] = False
+    cf = clean.view(np.float32).reshape(rows, -1)
+    df = dirty.view(np.float32).reshape(rows, -1)
+    assert np.isfinite(cf).all(), f"{what}: the clean batch gave non-finite outputs"
+    want = np.ldexp(cf, e[:, None]).view(np.uint32)
+    bad = np.nonzero((want[clean_mask] != df[clean_mask].view(np.uint32)).any(axis=1))[0]
+    assert bad.size == 0, f"{what}: unpoisoned rows {np.nonzero(clean_mask)[0][bad][:8].tolist()} are not 2^e x their clean rows"
+    for r, kind in kinds.items():
+        if real_out:
+            assert _non_finite(dirty[r]).all(), f"{what}: row {r} ({kind}) has finite outputs"
+            continue
+        nf_re, nf_im = _non_finite(dirty[r].real), _non_finite(dirty[r].imag)
+        if kind == "nan" and not real_in:
+            assert (nf_re & nf_im).all(), f"{what}: row {r} (complex NaN) has an output with a finite component"
+        else:
+            assert (nf_re | nf_im).all(), f"{what}: row {r} ({kind}) has a finite output"
 
 
 # ---------------------------------------------------------------------------------------------------- B: the FIR filter banks
