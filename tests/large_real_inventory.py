@@ -1,7 +1,9 @@
 """Every __global__ kernel that libsmfft_large_real.so ships (real N = 16384 / 32768 single-pass R2C / C2R, include/smfft_large_real.h),
 with the public call that reaches it and the GPU tests that compare it with fp64, run it on guarded buffers and probe it per element
-and in isolation.  tests/test_large_real_cpu.py checks this list against the built library's kernels, with the rule of
-tests/test_kernel_inventory.py.  Names are the demangled kernel names without their parameter lists; N is the real length."""
+and in isolation, and the CPU tests that run it on the host ("host").  tests/test_large_real_cpu.py checks this list against the built
+library's kernels, with the rule of tests/test_kernel_inventory.py.  Names are the demangled kernel names without their parameter lists; N is the real length."""
+
+from tests.large_inventory import HOST_TESTS      # the host run of the kernel (tests/hostsim), shared with the C2C kernels
 
 REAL = "tests/test_large_real_gpu.py::"
 _TESTS = [REAL + "test_large_real_parity", REAL + "test_large_real_round_trip", REAL + "test_large_real_caller_stream_ordering",
@@ -19,6 +21,7 @@ KERNELS = {
         "tests": _TESTS,
         "bounds": _BOUNDS,
         "probes": _PROBES[d] + _ISOLATION,
+        "host": HOST_TESTS,
     }
     for n in (16384, 32768) for d, name in ((0, "large_r2c"), (1, "large_c2r"))
 }

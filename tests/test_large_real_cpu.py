@@ -233,12 +233,13 @@ def test_every_large_real_kernel_is_in_the_inventory_with_its_tests(real_lib):
     assert handles == stubs and len(handles) == 4, (sorted(handles), sorted(stubs))
     assert handles == set(rinv.KERNELS), (sorted(handles ^ set(rinv.KERNELS)))
     for name, entry in rinv.KERNELS.items():
-        assert set(entry) == {"call", "tests", "bounds", "probes"}, name
+        assert set(entry) == {"call", "tests", "bounds", "probes", "host"}, name
         assert entry["call"].startswith("smfft_large_real_"), name
-        for key in ("tests", "bounds", "probes"):
+        for key in ("tests", "bounds", "probes", "host"):
             assert entry[key], (name, key)
             for tid in entry[key]:
                 m = re.fullmatch(r"(tests/test_\w+\.py)::(test_\w+)", tid)
                 assert m, tid
                 names, gpu = kinv._gpu_tests(os.path.join(ROOT, m.group(1)))
-                assert m.group(2) in names and gpu, tid
+                # "host": the run of the kernel on the host (tests/hostsim) belongs to the suite that needs no GPU
+                assert m.group(2) in names and gpu == (key != "host"), tid
