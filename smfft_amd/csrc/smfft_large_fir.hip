@@ -1,0 +1,147 @@
+// smfft_large_fir.hip -- libsmfft_large_fir.so: the overlap-save FIR filter banks with N = 8192 / 16384 segments and the C ABI of
+// include/smfft_large_fir.h.
+//
+// Compiled three times (Makefile): -DSMFFT_LARGE_FIR_N=8192 and -DSMFFT_LARGE_FIR_N=16384 give one object per length with its kernels
+// and its launchers (flags of their own: LARGE_FIR_FLAGS_<N>); without SMFFT_LARGE_FIR_N it is the C ABI, which only checks and
+// dispatches.
+//
+// The work split (include/smfft/smfft_large_fir.hpp has the two forms of the filter loop; DESIGN.md section 11 the measurement that
+// chose between them).  cus = the compute units of the device.
+//   * N = 16384, and N = 8192 with one filter: the RECOMPUTE form.  C S K units (segment, filter), filter fastest, on a persistent
+//     grid of min(units, cus x workgroups per CU) workgroups.
+//   * N = 8192 with K > 1: the HELD form, 25 % faster there.  C S segments x filter groups of
+//     smfft::fir_filter_group_size(C S, K, target) filters, target = that form's persistent grid (cus: one workgroup per CU) -- groups
+//     = min(K, ceil(cus / (C S))) -- so that a short signal with many filters still fills the chip and a long one pays one forward
+//     transform per segment.
+// -DSMFFT_LARGE_FIR_HELD_8192=0 (the A/B build of tools/ab_large_fir.py, never the shipped one) keeps N = 8192 on the recompute
+// form for every K.
+#include <hip/hip_runtime.h>
+
+#include "smfft_fir.hpp"
+#include "smfft_large_fir.h"
+
+namespace smfft {
+namespace large {
+// enqueue on `stream`; cus = compute units of the current device; 0 or the launch's hipError_t
+template <int N>
+int launch_fir(const float2* x, const float2* H, float2* y, const FirWindow& w, int C, int K, int cus, hipStream_t stream);
+template <int N>
+int launch_fir_prepare(const float2* taps, int M, int K, int correlate, float2* spectra, int cus, hipStream_t stream);
+}  // namespace large
+}  // namespace smfft
+
+#ifdef SMFFT_LARGE_FIR_N
+#include "smfft/smfft_large_fir.hpp"
+
+#ifndef SMFFT_LARGE_FIR_HELD_8192
+#define SMFFT_LARGE_FIR_HELD_8192 1
+#endif
+
+namespace smfft {
+namespace large {
+template <>
+int launch_fir<SMFFT_LARGE_FIR_N>(const float2* x, const float2* H, float2* y, const FirWindow& w, int C, int K, int cus, hipStream_t stream) {
+    constexpr int N = SMFFT_LARGE_FIR_N;
+    const long long segments = w.segments() * C;
+#if SMFFT_LARGE_FIR_HELD_8192 && SMFFT_LARGE_FIR_N == 8192
+    if (K > 1) {
+        const int group = fir_filter_group_size(segments, K, cus);
+        const int groups = (K + group - 1) / group;
+        const long long units = segments * groups;
+        const dim3 blocks((unsigned)(units < cus ? units : cus)), threads(N / 16);
+        hipLaunchKernelGGL((large_fir<8192, 1>), blocks, threads, 0, stream, x, H, y, w, K, group, units, large_fir_stride(blocks.x, groups, w.segments()));
+        return (int)hipGetLastError();
+    }
+#endif
+    const int grid = cus * LargeGeometry<N>::kWorkgroupsPerCu;
+    const long long units = segments * K;
+    const dim3 blocks((unsigned)(units < grid ? units : grid)), threads(N / 16);
+    hipLaunchKernelGGL((large_fir<N, 0>), blocks, threads, 0, stream, x, H, y, w, K, 1, units, large_fir_stride(blocks.x, K, w.segments()));
+    return (int)hipGetLastError();
+}
+
+template <>
+int launch_fir_prepare<SMFFT_LARGE_FIR_N>(const float2* taps, int M, int K, int correlate, float2* spectra, int cus, hipStream_t stream) {
+    constexpr int N = SMFFT_LARGE_FIR_N;
+    const int grid = cus * LargeGeometry<N>::kWorkgroupsPerCu;
+    const dim3 blocks(K < grid ? K : grid), threads(N / 16);
+    hipLaunchKernelGGL((large_fir_prepare<N>), blocks, threads, 0, stream, taps, M, K, correlate, spectra);
+    return (int)hipGetLastError();
+}
+}  // namespace large
+}  // namespace smfft
+
+#else  // the C ABI
+
+namespace {
+constexpr int kMaxDevices = 64;
+int g_cus[kMaxDevices];     // compute units per device, read once
+
+// compute units of the current device; 0 when it cannot be queried
+int compute_units() {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0) return 0;
+    int cus = dev < kMaxDevices ? __atomic_load_n(&g_cus[dev], __ATOMIC_RELAXED) : 0;
+    if (cus <= 0) {
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) return 0;
+        if (dev < kMaxDevices) __atomic_store_n(&g_cus[dev], cus, __ATOMIC_RELAXED);
+    }
+    return cus;
+}
+
+bool supported(int FFT_size) { return FFT_size == 8192 || FFT_size == 16384; }
+
+// -1: an unsupported combination; 0: launch; 1: nothing to do (an empty signal).  No HIP call.
+int check(long long L, int C, int K, int M, int N) {
+    if (!supported(N) || M < 1 || M >= N || C <= 0 || K <= 0 || L < 0) return -1;
+    return L == 0 ? 1 : 0;
+}
+
+int dispatch(const void* x, long long L, int C, const void* H, int K, int M, int N, int correlate, void* y, hipStream_t stream) {
+    const int cus = compute_units();
+    if (cus <= 0) return (int)hipErrorNoDevice;
+    const smfft::FirWindow w{L, N, M, correlate != 0};
+    if (N == 8192) return smfft::large::launch_fir<8192>((const float2*)x, (const float2*)H, (float2*)y, w, C, K, cus, stream);
+    return smfft::large::launch_fir<16384>((const float2*)x, (const float2*)H, (float2*)y, w, C, K, cus, stream);
+}
+}  // namespace
+
+extern "C" {
+
+int smfft_large_fir_prepare(const void* d_taps, int n_taps, int n_filters, int FFT_size, int correlate, void* d_spectra, void* hip_stream) {
+    if (!supported(FFT_size) || n_taps < 1 || n_taps >= FFT_size || n_filters <= 0) return -1;
+    const int cus = compute_units();
+    if (cus <= 0) return (int)hipErrorNoDevice;
+    const int c = correlate != 0;
+    if (FFT_size == 8192) return smfft::large::launch_fir_prepare<8192>((const float2*)d_taps, n_taps, n_filters, c, (float2*)d_spectra, cus, (hipStream_t)hip_stream);
+    return smfft::large::launch_fir_prepare<16384>((const float2*)d_taps, n_taps, n_filters, c, (float2*)d_spectra, cus, (hipStream_t)hip_stream);
+}
+
+int smfft_large_fir_launch(const void* d_signal, long long signal_length, int n_channels, const void* d_spectra, int n_filters, int n_taps,
+                           int FFT_size, int correlate, void* d_output, void* hip_stream) {
+    const int chk = check(signal_length, n_channels, n_filters, n_taps, FFT_size);
+    if (chk != 0) return chk < 0 ? -1 : 0;
+    return dispatch(d_signal, signal_length, n_channels, d_spectra, n_filters, n_taps, FFT_size, correlate, d_output, (hipStream_t)hip_stream);
+}
+
+int smfft_large_fir_benchmark(const void* d_signal, long long signal_length, int n_channels, const void* d_spectra, int n_filters, int n_taps,
+                              int FFT_size, int correlate, void* d_output, double* FFT_time) {
+    const int chk = check(signal_length, n_channels, n_filters, n_taps, FFT_size);
+    if (chk != 0) return chk < 0 ? -1 : 0;
+    hipEvent_t start = nullptr, stop = nullptr;
+    int rc = (int)hipEventCreate(&start);
+    if (rc == 0) rc = (int)hipEventCreate(&stop);
+    if (rc == 0) rc = (int)hipEventRecord(start, nullptr);
+    if (rc == 0) rc = dispatch(d_signal, signal_length, n_channels, d_spectra, n_filters, n_taps, FFT_size, correlate, d_output, nullptr);
+    if (rc == 0) rc = (int)hipEventRecord(stop, nullptr);
+    if (rc == 0) rc = (int)hipEventSynchronize(stop);
+    float ms = 0.f;
+    if (rc == 0) rc = (int)hipEventElapsedTime(&ms, start, stop);
+    if (rc == 0 && FFT_time) *FFT_time += ms;
+    if (start) (void)hipEventDestroy(start);
+    if (stop) (void)hipEventDestroy(stop);
+    return rc;
+}
+
+}  // extern "C"
+#endif
