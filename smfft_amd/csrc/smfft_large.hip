@@ -8,9 +8,12 @@
 
 namespace smfft {
 namespace large {
-// enqueue N-point transforms of nFFTs > 0 FFTs on `stream`; 0 or the launch's hipError_t
+// the persistent grid of N on a device of `cus` compute units: cus x workgroups per CU
 template <int N>
-int launch(const float2* d_input, float2* d_output, int nFFTs, bool inverse, int grid, hipStream_t stream);
+int grid(int cus);
+// enqueue N-point transforms of nFFTs > 0 FFTs on `stream`, on min(grid<N>(cus), nFFTs) workgroups; 0 or the launch's hipError_t
+template <int N>
+int launch(const float2* d_input, float2* d_output, int nFFTs, bool inverse, int cus, hipStream_t stream);
 }  // namespace large
 }  // namespace smfft
 
@@ -20,9 +23,15 @@ int launch(const float2* d_input, float2* d_output, int nFFTs, bool inverse, int
 namespace smfft {
 namespace large {
 template <>
-int launch<SMFFT_LARGE_N>(const float2* d_input, float2* d_output, int nFFTs, bool inverse, int grid, hipStream_t stream) {
+int grid<SMFFT_LARGE_N>(int cus) {
+    return cus * LargeGeometry<SMFFT_LARGE_N>::kWorkgroupsPerCu;
+}
+
+template <>
+int launch<SMFFT_LARGE_N>(const float2* d_input, float2* d_output, int nFFTs, bool inverse, int cus, hipStream_t stream) {
     constexpr int N = SMFFT_LARGE_N;
-    const dim3 blocks(grid < nFFTs ? grid : nFFTs), threads(N / 16);
+    const int g = grid<N>(cus);
+    const dim3 blocks(g < nFFTs ? g : nFFTs), threads(N / 16);
     if (inverse) hipLaunchKernelGGL((large_c2c<N, 1>), blocks, threads, 0, stream, d_input, d_output, nFFTs);
     else hipLaunchKernelGGL((large_c2c<N, 0>), blocks, threads, 0, stream, d_input, d_output, nFFTs);
     return (int)hipGetLastError();
@@ -31,32 +40,18 @@ int launch<SMFFT_LARGE_N>(const float2* d_input, float2* d_output, int nFFTs, bo
 }  // namespace smfft
 
 #else  // the C ABI
+#include "smfft_addon_host.hpp"
 
 namespace {
-constexpr int kMaxDevices = 64;
-int g_cus[kMaxDevices];     // compute units per device, read once
-
-// the persistent grid of FFT_size on the current device: CUs x workgroups per CU; 0 when the device cannot be queried
-int persistent_grid(int FFT_size) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0) return 0;
-    int cus = dev < kMaxDevices ? __atomic_load_n(&g_cus[dev], __ATOMIC_RELAXED) : 0;
-    if (cus <= 0) {
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) return 0;
-        if (dev < kMaxDevices) __atomic_store_n(&g_cus[dev], cus, __ATOMIC_RELAXED);
-    }
-    return cus * (FFT_size == 8192 ? 2 : 1);
-}
-
 bool supported(int FFT_size) { return FFT_size == 8192 || FFT_size == 16384; }
 
 int dispatch(const void* d_input, void* d_output, int FFT_size, int nFFTs, int inverse, hipStream_t stream) {
-    const int grid = persistent_grid(FFT_size);
-    if (grid <= 0) return (int)hipErrorNoDevice;
+    const int cus = compute_units();
+    if (cus <= 0) return (int)hipErrorNoDevice;
     const float2* in = (const float2*)d_input;
     float2* out = (float2*)d_output;
-    if (FFT_size == 8192) return smfft::large::launch<8192>(in, out, nFFTs, inverse != 0, grid, stream);
-    return smfft::large::launch<16384>(in, out, nFFTs, inverse != 0, grid, stream);
+    if (FFT_size == 8192) return smfft::large::launch<8192>(in, out, nFFTs, inverse != 0, cus, stream);
+    return smfft::large::launch<16384>(in, out, nFFTs, inverse != 0, cus, stream);
 }
 }  // namespace
 
@@ -71,24 +66,13 @@ int smfft_large_launch(const void* d_input, void* d_output, int FFT_size, int nF
 int smfft_large_benchmark(const void* d_input, void* d_output, int FFT_size, int nFFTs, int inverse, double* FFT_time) {
     if (!supported(FFT_size) || nFFTs < 0) return -1;
     if (nFFTs == 0) return 0;
-    hipEvent_t start = nullptr, stop = nullptr;
-    int rc = (int)hipEventCreate(&start);
-    if (rc == 0) rc = (int)hipEventCreate(&stop);
-    if (rc == 0) rc = (int)hipEventRecord(start, nullptr);
-    if (rc == 0) rc = dispatch(d_input, d_output, FFT_size, nFFTs, inverse, nullptr);
-    if (rc == 0) rc = (int)hipEventRecord(stop, nullptr);
-    if (rc == 0) rc = (int)hipEventSynchronize(stop);
-    float ms = 0.f;
-    if (rc == 0) rc = (int)hipEventElapsedTime(&ms, start, stop);
-    if (rc == 0 && FFT_time) *FFT_time += ms;
-    if (start) (void)hipEventDestroy(start);
-    if (stop) (void)hipEventDestroy(stop);
-    return rc;
+    return timed_launch(FFT_time, [&] { return dispatch(d_input, d_output, FFT_size, nFFTs, inverse, nullptr); });
 }
 
 int smfft_large_grid(int FFT_size) {
     if (!supported(FFT_size)) return -1;
-    return persistent_grid(FFT_size);
+    const int cus = compute_units();      // 0 when the device cannot be queried, and so is the grid then
+    return FFT_size == 8192 ? smfft::large::grid<8192>(cus) : smfft::large::grid<16384>(cus);
 }
 
 }  // extern "C"

@@ -72,23 +72,9 @@ int launch_fir_prepare<SMFFT_LARGE_FIR_N>(const float2* taps, int M, int K, int 
 }  // namespace smfft
 
 #else  // the C ABI
+#include "smfft_addon_host.hpp"
 
 namespace {
-constexpr int kMaxDevices = 64;
-int g_cus[kMaxDevices];     // compute units per device, read once
-
-// compute units of the current device; 0 when it cannot be queried
-int compute_units() {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0) return 0;
-    int cus = dev < kMaxDevices ? __atomic_load_n(&g_cus[dev], __ATOMIC_RELAXED) : 0;
-    if (cus <= 0) {
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) return 0;
-        if (dev < kMaxDevices) __atomic_store_n(&g_cus[dev], cus, __ATOMIC_RELAXED);
-    }
-    return cus;
-}
-
 bool supported(int FFT_size) { return FFT_size == 8192 || FFT_size == 16384; }
 
 // -1: an unsupported combination; 0: launch; 1: nothing to do (an empty signal).  No HIP call.
@@ -128,19 +114,7 @@ int smfft_large_fir_benchmark(const void* d_signal, long long signal_length, int
                               int FFT_size, int correlate, void* d_output, double* FFT_time) {
     const int chk = check(signal_length, n_channels, n_filters, n_taps, FFT_size);
     if (chk != 0) return chk < 0 ? -1 : 0;
-    hipEvent_t start = nullptr, stop = nullptr;
-    int rc = (int)hipEventCreate(&start);
-    if (rc == 0) rc = (int)hipEventCreate(&stop);
-    if (rc == 0) rc = (int)hipEventRecord(start, nullptr);
-    if (rc == 0) rc = dispatch(d_signal, signal_length, n_channels, d_spectra, n_filters, n_taps, FFT_size, correlate, d_output, nullptr);
-    if (rc == 0) rc = (int)hipEventRecord(stop, nullptr);
-    if (rc == 0) rc = (int)hipEventSynchronize(stop);
-    float ms = 0.f;
-    if (rc == 0) rc = (int)hipEventElapsedTime(&ms, start, stop);
-    if (rc == 0 && FFT_time) *FFT_time += ms;
-    if (start) (void)hipEventDestroy(start);
-    if (stop) (void)hipEventDestroy(stop);
-    return rc;
+    return timed_launch(FFT_time, [&] { return dispatch(d_signal, signal_length, n_channels, d_spectra, n_filters, n_taps, FFT_size, correlate, d_output, nullptr); });
 }
 
 }  // extern "C"

@@ -10,9 +10,13 @@
 
 namespace smfft {
 namespace large {
-// enqueue real N-point transforms of nFFTs > 0 FFTs on `stream`; 0 or the launch's hipError_t
+// the persistent grid of real N on a device of `cus` compute units: cus x workgroups per CU
 template <int N>
-int launch_real(const void* d_input, void* d_output, int nFFTs, bool inverse, int grid, hipStream_t stream);
+int grid_real(int cus);
+// enqueue real N-point transforms of nFFTs > 0 FFTs on `stream`, on min(grid_real<N>(cus), nFFTs) workgroups; 0 or the launch's
+// hipError_t
+template <int N>
+int launch_real(const void* d_input, void* d_output, int nFFTs, bool inverse, int cus, hipStream_t stream);
 }  // namespace large
 }  // namespace smfft
 
@@ -22,9 +26,15 @@ int launch_real(const void* d_input, void* d_output, int nFFTs, bool inverse, in
 namespace smfft {
 namespace large {
 template <>
-int launch_real<SMFFT_LARGE_REAL_N>(const void* d_input, void* d_output, int nFFTs, bool inverse, int grid, hipStream_t stream) {
+int grid_real<SMFFT_LARGE_REAL_N>(int cus) {
+    return cus * LargeRealGeometry<SMFFT_LARGE_REAL_N>::G::kWorkgroupsPerCu;      // (the complex engine of N / 2 points)
+}
+
+template <>
+int launch_real<SMFFT_LARGE_REAL_N>(const void* d_input, void* d_output, int nFFTs, bool inverse, int cus, hipStream_t stream) {
     constexpr int N = SMFFT_LARGE_REAL_N;
-    const dim3 blocks(grid < nFFTs ? grid : nFFTs), threads(N / 32);
+    const int g = grid_real<N>(cus);
+    const dim3 blocks(g < nFFTs ? g : nFFTs), threads(N / 32);
     if (inverse) hipLaunchKernelGGL((large_c2r<N>), blocks, threads, 0, stream, (const float2*)d_input, (float*)d_output, nFFTs);
     else hipLaunchKernelGGL((large_r2c<N>), blocks, threads, 0, stream, (const float*)d_input, (float2*)d_output, nFFTs);
     return (int)hipGetLastError();
@@ -33,30 +43,16 @@ int launch_real<SMFFT_LARGE_REAL_N>(const void* d_input, void* d_output, int nFF
 }  // namespace smfft
 
 #else  // the C ABI
+#include "smfft_addon_host.hpp"
 
 namespace {
-constexpr int kMaxDevices = 64;
-int g_cus[kMaxDevices];     // compute units per device, read once
-
-// the persistent grid of FFT_size on the current device: CUs x workgroups per CU; 0 when the device cannot be queried
-int persistent_grid(int FFT_size) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0) return 0;
-    int cus = dev < kMaxDevices ? __atomic_load_n(&g_cus[dev], __ATOMIC_RELAXED) : 0;
-    if (cus <= 0) {
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) return 0;
-        if (dev < kMaxDevices) __atomic_store_n(&g_cus[dev], cus, __ATOMIC_RELAXED);
-    }
-    return cus * (FFT_size == 16384 ? 2 : 1);
-}
-
 bool supported(int FFT_size) { return FFT_size == 16384 || FFT_size == 32768; }
 
 int dispatch(const void* d_input, void* d_output, int FFT_size, int nFFTs, int inverse, hipStream_t stream) {
-    const int grid = persistent_grid(FFT_size);
-    if (grid <= 0) return (int)hipErrorNoDevice;
-    if (FFT_size == 16384) return smfft::large::launch_real<16384>(d_input, d_output, nFFTs, inverse != 0, grid, stream);
-    return smfft::large::launch_real<32768>(d_input, d_output, nFFTs, inverse != 0, grid, stream);
+    const int cus = compute_units();
+    if (cus <= 0) return (int)hipErrorNoDevice;
+    if (FFT_size == 16384) return smfft::large::launch_real<16384>(d_input, d_output, nFFTs, inverse != 0, cus, stream);
+    return smfft::large::launch_real<32768>(d_input, d_output, nFFTs, inverse != 0, cus, stream);
 }
 }  // namespace
 
@@ -71,24 +67,13 @@ int smfft_large_real_launch(const void* d_input, void* d_output, int FFT_size, i
 int smfft_large_real_benchmark(const void* d_input, void* d_output, int FFT_size, int nFFTs, int inverse, double* FFT_time) {
     if (!supported(FFT_size) || nFFTs < 0) return -1;
     if (nFFTs == 0) return 0;
-    hipEvent_t start = nullptr, stop = nullptr;
-    int rc = (int)hipEventCreate(&start);
-    if (rc == 0) rc = (int)hipEventCreate(&stop);
-    if (rc == 0) rc = (int)hipEventRecord(start, nullptr);
-    if (rc == 0) rc = dispatch(d_input, d_output, FFT_size, nFFTs, inverse, nullptr);
-    if (rc == 0) rc = (int)hipEventRecord(stop, nullptr);
-    if (rc == 0) rc = (int)hipEventSynchronize(stop);
-    float ms = 0.f;
-    if (rc == 0) rc = (int)hipEventElapsedTime(&ms, start, stop);
-    if (rc == 0 && FFT_time) *FFT_time += ms;
-    if (start) (void)hipEventDestroy(start);
-    if (stop) (void)hipEventDestroy(stop);
-    return rc;
+    return timed_launch(FFT_time, [&] { return dispatch(d_input, d_output, FFT_size, nFFTs, inverse, nullptr); });
 }
 
 int smfft_large_real_grid(int FFT_size) {
     if (!supported(FFT_size)) return -1;
-    return persistent_grid(FFT_size);
+    const int cus = compute_units();      // 0 when the device cannot be queried, and so is the grid then
+    return FFT_size == 16384 ? smfft::large::grid_real<16384>(cus) : smfft::large::grid_real<32768>(cus);
 }
 
 }  // extern "C"

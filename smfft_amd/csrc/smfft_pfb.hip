@@ -121,23 +121,9 @@ int launch<SMFFT_PFB_N>(const float2* x, const float* h, void* y, const PfbPlan&
 }  // namespace smfft
 
 #else  // the C ABI
+#include "smfft_addon_host.hpp"
 
 namespace {
-constexpr int kMaxDevices = 64;
-int g_cus[kMaxDevices];     // compute units per device, read once
-
-// compute units of the current device; 0 when it cannot be queried
-int compute_units() {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0) return 0;
-    int cus = dev < kMaxDevices ? __atomic_load_n(&g_cus[dev], __ATOMIC_RELAXED) : 0;
-    if (cus <= 0) {
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) return 0;
-        if (dev < kMaxDevices) __atomic_store_n(&g_cus[dev], cus, __ATOMIC_RELAXED);
-    }
-    return cus;
-}
-
 bool supported(int N, int P) { return (N == 256 || N == 512 || N == 1024 || N == 2048 || N == 4096) && P >= 1 && P <= 32; }
 
 // the shipped run length of the schedule: a starting value, the same for every (N, P), until tools/ab_pfb.py has been run on a device
@@ -200,19 +186,7 @@ int smfft_pfb_benchmark(const void* d_signal, long long signal_length, int n_str
                         int power, void* d_output, double* FFT_time) {
     const int chk = check(signal_length, n_streams, n_channels, taps_per_channel, 0);
     if (chk != 0) return chk < 0 ? -1 : 0;
-    hipEvent_t start = nullptr, stop = nullptr;
-    int rc = (int)hipEventCreate(&start);
-    if (rc == 0) rc = (int)hipEventCreate(&stop);
-    if (rc == 0) rc = (int)hipEventRecord(start, nullptr);
-    if (rc == 0) rc = dispatch(d_signal, signal_length, n_streams, d_taps, n_channels, taps_per_channel, power, d_output, 0, nullptr);
-    if (rc == 0) rc = (int)hipEventRecord(stop, nullptr);
-    if (rc == 0) rc = (int)hipEventSynchronize(stop);
-    float ms = 0.f;
-    if (rc == 0) rc = (int)hipEventElapsedTime(&ms, start, stop);
-    if (rc == 0 && FFT_time) *FFT_time += ms;
-    if (start) (void)hipEventDestroy(start);
-    if (stop) (void)hipEventDestroy(stop);
-    return rc;
+    return timed_launch(FFT_time, [&] { return dispatch(d_signal, signal_length, n_streams, d_taps, n_channels, taps_per_channel, power, d_output, 0, nullptr); });
 }
 
 }  // extern "C"

@@ -5,12 +5,12 @@ plain integers; transforms are un-normalised, natural order in and out; timings 
 There is no CPU fallback: a missing library raises on first call.
 """
 import ctypes
-import os
 
 import numpy as np
 
+from . import _addon
+
 SIZES = (8192, 16384)
-LIB_PATH = os.environ.get("SMFFT_LARGE_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libsmfft_large.so")
 
 _vp, _i, _dp = ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_double)
 # name -> (restype, argtypes), exactly the declarations of include/smfft_large.h (tests/test_large_cpu.py compares them)
@@ -20,22 +20,8 @@ SIGS = {
     "smfft_large_grid": (_i, [_i]),
 }
 
+LIB_PATH, load, lib = _addon.loader("libsmfft_large.so", "SMFFT_LARGE_LIB", __name__, SIGS)
 _lib = None
-
-
-def lib():
-    """the loaded libsmfft_large.so (loaded and typed on the first call)"""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise ImportError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                              "(or `make -C smfft_amd/csrc`).  smfft_amd.large has no CPU fallback.")
-        handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGS.items():
-            fn = getattr(handle, name)
-            fn.restype, fn.argtypes = res, args
-        _lib = handle
-    return _lib
 
 
 def launch(d_in, d_out, N, nFFTs, inverse=False, stream=0):
@@ -70,4 +56,7 @@ def c2c(x, inverse=False):
     rc, _ = benchmark(din.ptr, dout.ptr, n, nffts, inverse)
     if rc != 0:
         raise RuntimeError(f"smfft_large_benchmark(N={n}, nFFTs={nffts}) -> {rc}")
-    return dout.to_host(np.complex64, x.shape)
+    out = dout.to_host(np.complex64, x.shape)
+    for b in (din, dout):
+        b.free()
+    return out

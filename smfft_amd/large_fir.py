@@ -6,12 +6,12 @@ plain integers; the semantics, layouts and spectra format are those of smfft_amd
 running total, as in smfft_amd.api.  There is no CPU fallback: a missing library raises on first call.
 """
 import ctypes
-import os
 
 import numpy as np
 
+from . import _addon
+
 SIZES = (8192, 16384)
-LIB_PATH = os.environ.get("SMFFT_LARGE_FIR_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libsmfft_large_fir.so")
 
 _vp, _i, _ll, _dp = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.POINTER(ctypes.c_double)
 # name -> (restype, argtypes), exactly the declarations of include/smfft_large_fir.h (tests/test_large_fir_cpu.py compares them)
@@ -21,22 +21,8 @@ SIGS = {
     "smfft_large_fir_benchmark": (_i, [_vp, _ll, _i, _vp, _i, _i, _i, _i, _vp, _dp]),
 }
 
+LIB_PATH, load, lib = _addon.loader("libsmfft_large_fir.so", "SMFFT_LARGE_FIR_LIB", __name__, SIGS)
 _lib = None
-
-
-def lib():
-    """the loaded libsmfft_large_fir.so (loaded and typed on the first call)"""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise ImportError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                              "(or `make -C smfft_amd/csrc`).  smfft_amd.large_fir has no CPU fallback.")
-        handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGS.items():
-            fn = getattr(handle, name)
-            fn.restype, fn.argtypes = res, args
-        _lib = handle
-    return _lib
 
 
 def _mode(mode):
@@ -102,4 +88,7 @@ def fir(x, taps, mode="convolve", fft_size=None):
         rc = api.lib.smfft_synchronize()
     if rc != 0:
         raise RuntimeError(f"large_fir.fir(C={C}, L={L}, K={K}, M={M}, N={N}, {mode}) -> {rc}")
-    return dout.to_host(np.complex64, (C, K, L))
+    out = dout.to_host(np.complex64, (C, K, L))
+    for b in (din, dtaps, dspec, dout):
+        b.free()
+    return out

@@ -7,12 +7,12 @@ reads that layout and writes (N/2) x -- the conventions of smfft_rc_external_ben
 smfft_amd.api.  There is no CPU fallback: a missing library raises on first call.
 """
 import ctypes
-import os
 
 import numpy as np
 
+from . import _addon
+
 SIZES = (16384, 32768)
-LIB_PATH = os.environ.get("SMFFT_LARGE_REAL_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libsmfft_large_real.so")
 
 _vp, _i, _dp = ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_double)
 # name -> (restype, argtypes), exactly the declarations of include/smfft_large_real.h (tests/test_large_real_cpu.py compares them)
@@ -22,22 +22,8 @@ SIGS = {
     "smfft_large_real_grid": (_i, [_i]),
 }
 
+LIB_PATH, load, lib = _addon.loader("libsmfft_large_real.so", "SMFFT_LARGE_REAL_LIB", __name__, SIGS)
 _lib = None
-
-
-def lib():
-    """the loaded libsmfft_large_real.so (loaded and typed on the first call)"""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise ImportError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                              "(or `make -C smfft_amd/csrc`).  smfft_amd.large_real has no CPU fallback.")
-        handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGS.items():
-            fn = getattr(handle, name)
-            fn.restype, fn.argtypes = res, args
-        _lib = handle
-    return _lib
 
 
 def launch(d_in, d_out, N, nFFTs, inverse=False, stream=0):
@@ -67,7 +53,10 @@ def _run(x, out_dtype, out_shape, n, inverse):
     rc, _ = benchmark(din.ptr, dout.ptr, n, x.shape[0], inverse)
     if rc != 0:
         raise RuntimeError(f"smfft_large_real_benchmark(N={n}, nFFTs={x.shape[0]}, inverse={int(inverse)}) -> {rc}")
-    return dout.to_host(out_dtype, out_shape)
+    out = dout.to_host(out_dtype, out_shape)
+    for b in (din, dout):
+        b.free()
+    return out
 
 
 def r2c(x):

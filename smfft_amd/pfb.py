@@ -6,13 +6,13 @@ plain integers; timings are ADDED to a running total, as in smfft_amd.api.  Ther
 first call.
 """
 import ctypes
-import os
 
 import numpy as np
 
+from . import _addon
+
 SIZES = (256, 512, 1024, 2048, 4096)
 MAX_TAPS_PER_CHANNEL = 32
-LIB_PATH = os.environ.get("SMFFT_PFB_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libsmfft_pfb.so")
 
 _vp, _i, _ll, _dp = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.POINTER(ctypes.c_double)
 # name -> (restype, argtypes), exactly the declarations of include/smfft_pfb.h (tests/test_pfb_cpu.py compares them)
@@ -24,27 +24,8 @@ SIGS = {
     "smfft_pfb_default_tile_run": (_i, [_i, _i]),
 }
 
+LIB_PATH, load, lib = _addon.loader("libsmfft_pfb.so", "SMFFT_PFB_LIB", __name__, SIGS)
 _lib = None
-
-
-def load(path):
-    """a typed handle of the libsmfft_pfb.so at `path` (tools/ab_pfb.py loads a second build beside the shipped one)"""
-    handle = ctypes.CDLL(path)
-    for name, (res, args) in SIGS.items():
-        fn = getattr(handle, name)
-        fn.restype, fn.argtypes = res, args
-    return handle
-
-
-def lib():
-    """the loaded libsmfft_pfb.so (loaded and typed on the first call)"""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise ImportError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                              "(or `make -C smfft_amd/csrc`).  smfft_amd.pfb has no CPU fallback.")
-        _lib = load(LIB_PATH)
-    return _lib
 
 
 def frames(L, n_channels, taps_per_channel):

@@ -17,8 +17,8 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 import gen_twiddles_16384  # noqa: E402
 import large_plan_model as lpm  # noqa: E402
 
+from tests import addon_checks as ac  # noqa: E402
 from tests import large_inventory as linv  # noqa: E402
-from tests import test_kernel_inventory as kinv  # noqa: E402
 
 HIPCC = "/opt/rocm/bin/hipcc"
 CSRC = os.path.join(ROOT, "smfft_amd", "csrc")
@@ -127,49 +127,28 @@ def test_committed_octant_is_the_generators_output():
 
 
 # ---- ISA of what ships -------------------------------------------------------------------------------
-def _makefile_flags(n):
-    for line in open(os.path.join(CSRC, "Makefile")):
-        m = re.match(rf"LARGE_FLAGS_{n}\s*:=(.*)", line)
-        if m:
-            return m.group(1).split()
-    raise AssertionError(f"LARGE_FLAGS_{n} missing from the Makefile")
-
-
 @needs_hipcc
 @pytest.mark.parametrize("n", SIZES)
 def test_isa_budget(tmp_path, n):
-    out = tmp_path / f"large_{n}.s"
-    p = subprocess.run([HIPCC, "-O3", "--offload-arch=gfx950", "-std=c++17", "-fno-slp-vectorize", "-I" + os.path.join(ROOT, "include")]
-                       + _makefile_flags(n) + [f"-DSMFFT_LARGE_N={n}", "-S", "--cuda-device-only", os.path.join(CSRC, "smfft_large.hip"), "-o", str(out)],
-                       capture_output=True, text=True)
-    assert p.returncode == 0, p.stderr[-2000:]
-    text = out.read_text()
-    kernels = re.findall(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", text, flags=re.S)
+    text = ac.device_asm(os.path.join(CSRC, "smfft_large.hip"), ac.makefile_flags("LARGE", n) + [f"-DSMFFT_LARGE_N={n}"], tmp_path / f"large_{n}.s")
+    kernels = ac.descriptors(text)
     assert len(kernels) == 2
-    for name, desc in kernels:
-        field = lambda key: int(re.search(rf"\.{key} (\d+)", desc).group(1))  # noqa: E731
-        assert field("amdhsa_private_segment_fixed_size") == 0, name
-        lds = field("amdhsa_group_segment_fixed_size")
+    for name in kernels:
+        assert ac.descriptor_field(kernels, name, "private_segment_fixed_size") == 0, name
+        lds = ac.descriptor_field(kernels, name, "group_segment_fixed_size")
         assert lds <= 163840 and (n != 8192 or lds <= 81920), (name, lds)
-        assert field("amdhsa_next_free_vgpr") <= 128, name
+        assert ac.descriptor_field(kernels, name, "next_free_vgpr") <= 128, name
     assert not re.search(r"\bv_(sin|cos)_", text)
     assert not re.search(r"\bv_pk_(add|mul|fma)_f32", text)
 
 
 # ---- C ABI and Python mirror ---------------------------------------------------------------------------
-def _declared():
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "smfft_large.h")).read(), flags=re.S)
-    return dict(re.findall(r"\bint\s+(smfft_large_[a-z_]+)\s*\(([^)]*)\)", text))
-
-
 def test_python_mirror_matches_header(large_lib):
     from smfft_amd import large
-    decl = _declared()
+    decl = ac.declarations("smfft_large.h")
     assert sorted(decl) == sorted(large.SIGS)
-    kinds = {"const void*": ctypes.c_void_p, "void*": ctypes.c_void_p, "int": ctypes.c_int, "double*": ctypes.POINTER(ctypes.c_double)}
-    for name, args in decl.items():
-        types = [kinds[re.sub(r"\s*\w+$", "", a.strip())] for a in args.split(",")]
-        assert large.SIGS[name] == (ctypes.c_int, types), name
+    for name, (res, args) in decl.items():
+        assert res == "int" and large.SIGS[name] == ac.signature(res, args), name
     lib = ctypes.CDLL(large_lib)
     for name in decl:
         assert hasattr(lib, name), name
@@ -200,17 +179,4 @@ def test_import_does_not_load_the_large_library():
 
 # ---- kernel inventory of libsmfft_large.so ---------------------------------------------------------------
 def test_every_large_kernel_is_in_the_inventory_with_its_tests(large_lib):
-    handles, stubs = kinv._shipped_kernels(large_lib)
-    assert handles == stubs and len(handles) == 4, (sorted(handles), sorted(stubs))
-    assert handles == set(linv.KERNELS), (sorted(handles ^ set(linv.KERNELS)))
-    for name, entry in linv.KERNELS.items():
-        assert set(entry) == {"call", "tests", "bounds", "probes", "host"}, name
-        assert entry["call"].startswith("smfft_large_"), name
-        for key in ("tests", "bounds", "probes", "host"):
-            assert entry[key], (name, key)
-            for tid in entry[key]:
-                m = re.fullmatch(r"(tests/test_\w+\.py)::(test_\w+)", tid)
-                assert m, tid
-                names, gpu = kinv._gpu_tests(os.path.join(ROOT, m.group(1)))
-                # "host": the run of the kernel on the host (tests/hostsim) belongs to the suite that needs no GPU
-                assert m.group(2) in names and gpu == (key != "host"), tid
+    ac.check_inventory(large_lib, linv.KERNELS, "smfft_large_", 4)

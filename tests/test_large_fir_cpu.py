@@ -3,7 +3,6 @@ libsmfft_large_fir.so): the fp64 model of the plan (tools/large_fir_model.py) is
 the output once, smfft::FirWindow compiled for the host gives the model's windows at these lengths, the gfx950 code of every kernel --
 the ones the library ships and the other form of the filter loop, compiled from the header -- keeps the budgets of DESIGN.md section 11,
 and the C ABI declares, exports and validates the entry points without a device.  No GPU code is run (hipcc cross-compiles gfx950)."""
-import ctypes
 import os
 import re
 import subprocess
@@ -15,6 +14,8 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import large_fir_model as lfm  # noqa: E402
+
+from tests import addon_checks as ac  # noqa: E402
 
 HIPCC = "/opt/rocm/bin/hipcc"
 CSRC = os.path.join(ROOT, "smfft_amd", "csrc")
@@ -117,7 +118,6 @@ int main() {
 
 
 # ---- ISA ---------------------------------------------------------------------------------------------------
-FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fno-slp-vectorize", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC]
 FIR_ARGS = "PK15HIP_vector_typeIfLj2EES5_PS3_NS_9FirWindowEiixNS0_14LargeFirStrideE"
 PREPARE_ARGS = "PK15HIP_vector_typeIfLj2EEiiiPS3_"
 
@@ -130,32 +130,21 @@ def _prepare_name(n):
     return f"_ZN5smfft5large17large_fir_prepareILi{n}EEEv{PREPARE_ARGS}"
 
 
-def _makefile_flags(n):
-    for line in open(os.path.join(CSRC, "Makefile")):
-        m = re.match(rf"LARGE_FIR_FLAGS_{n}\s*:=(.*)", line)
-        if m:
-            return m.group(1).split()
-    raise AssertionError(f"LARGE_FIR_FLAGS_{n} missing from the Makefile")
-
-
-def _compile(tmp_path, src, extra, tag):
-    out = tmp_path / f"{tag}.s"
-    p = subprocess.run([HIPCC] + FLAGS + extra + ["-S", "--cuda-device-only", str(src), "-o", str(out)], capture_output=True, text=True)
-    assert p.returncode == 0, p.stderr[-2000:]
-    return out.read_text()
+def _compile(tmp_path, src, n, extra, tag):
+    """src as the Makefile compiles the object of length n: -I. and LARGE_FIR_FLAGS_<n>"""
+    return ac.device_asm(src, ["-I" + CSRC] + ac.makefile_flags("LARGE_FIR", n) + extra, tmp_path / f"{tag}.s")
 
 
 def _check_kernel(text, name, n, vgpr_cap, fir):
-    desc = re.search(r"\.amdhsa_kernel %s\n(.*?)\.end_amdhsa_kernel" % re.escape(name), text, re.S)
-    assert desc, name
-    field = lambda key: int(re.search(rf"\.{key} (\d+)", desc.group(1)).group(1))  # noqa: E731
+    descs = ac.descriptors(text)
+    field = lambda key: ac.descriptor_field(descs, name, key)  # noqa: E731
     body = re.search(r"^%s:[^\n]*\n(.*?)\n\s*s_endpgm" % re.escape(name), text, re.S | re.M)
     assert body, name
     lines = [line.strip() for line in body.group(1).split("\n")]
-    assert field("amdhsa_private_segment_fixed_size") == 0, name
+    assert field("private_segment_fixed_size") == 0, name
     assert not [line for line in lines if line.startswith("scratch_")], name
-    assert field("amdhsa_group_segment_fixed_size") == LDS_BYTES[n], name
-    vgprs = field("amdhsa_next_free_vgpr")
+    assert field("group_segment_fixed_size") == LDS_BYTES[n], name
+    vgprs = field("next_free_vgpr")
     assert vgprs <= vgpr_cap, (name, vgprs)
     assert not [line for line in lines if re.match(r"v_(sin|cos)_", line)], name
     assert not [line for line in lines if re.match(r"v_pk_(add|mul|fma)_f32", line)], name
@@ -174,7 +163,7 @@ def _check_kernel(text, name, n, vgpr_cap, fir):
 @pytest.mark.parametrize("n", SIZES)
 def test_isa_budget_of_what_ships(tmp_path, n):
     """the object of length n as the Makefile compiles it: the recompute form, the prepare kernel and, at 8192, the held form"""
-    text = _compile(tmp_path, os.path.join(CSRC, "smfft_large_fir.hip"), _makefile_flags(n) + [f"-DSMFFT_LARGE_FIR_N={n}"], f"large_fir_{n}")
+    text = _compile(tmp_path, os.path.join(CSRC, "smfft_large_fir.hip"), n, [f"-DSMFFT_LARGE_FIR_N={n}"], f"large_fir_{n}")
     kernels = re.findall(r"\.amdhsa_kernel (\S+)", text)
     assert sorted(kernels) == sorted([_fir_name(n, 0), _prepare_name(n)] + ([_fir_name(n, 1)] if n == 8192 else []))
     v = _check_kernel(text, _fir_name(n, 0), n, 128, True)
@@ -195,7 +184,7 @@ def test_isa_budget_of_the_held_form(tmp_path):
     src.write_text('#include "smfft/smfft_large_fir.hpp"\n'
                    "template __global__ void smfft::large::large_fir<8192, 1>(const float2*, const float2*, float2*, smfft::FirWindow, int, int, long long,\n"
                    "                                                          smfft::large::LargeFirStride);\n")
-    text = _compile(tmp_path, src, _makefile_flags(8192), "held")
+    text = _compile(tmp_path, src, 8192, [], "held")
     assert re.findall(r"\.amdhsa_kernel (\S+)", text) == [_fir_name(8192, 1)]
     v = _check_kernel(text, _fir_name(8192, 1), 8192, 256, True)
     print(f"large_fir<8192, 1> {v} VGPRs")
@@ -212,24 +201,16 @@ def test_shipped_library_holds_these_kernels(fir_lib):
 
 
 # ---- C ABI and Python mirror ---------------------------------------------------------------------------------
-def _declared():
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "smfft_large_fir.h")).read(), flags=re.S)
-    return dict(re.findall(r"\bint\s+(smfft_large_fir_[a-z_]+)\s*\(([^)]*)\)", text))
-
-
 def test_python_mirror_matches_header(fir_lib):
     from smfft_amd import large_fir
-    decl = _declared()
+    decl = ac.declarations("smfft_large_fir.h")
     assert sorted(decl) == sorted(large_fir.SIGS) == sorted(NAMES)
-    kinds = {"const void*": ctypes.c_void_p, "void*": ctypes.c_void_p, "int": ctypes.c_int, "long long": ctypes.c_longlong,
-             "double*": ctypes.POINTER(ctypes.c_double)}
-    for name, args in decl.items():
-        types = [kinds[re.sub(r"\s*\w+$", "", a.strip())] for a in args.split(",")]
-        assert large_fir.SIGS[name] == (ctypes.c_int, types), name
+    for name, (res, args) in decl.items():
+        assert res == "int" and large_fir.SIGS[name] == ac.signature(res, args), name
     assert large_fir.SIZES == SIZES
     # the declarations are those of the FIR block of include/smfft.h, word for word, under the new names
     base = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "smfft.h")).read(), flags=re.S)
-    for name, args in decl.items():
+    for name, (_, args) in decl.items():
         m = re.search(r"\bint\s+%s\s*\(([^)]*)\)" % name.replace("smfft_large_fir_", "smfft_fir_"), base)
         assert m and re.sub(r"\s+", " ", m.group(1)) == re.sub(r"\s+", " ", args), name
 

@@ -20,8 +20,8 @@ import large_plan_model as lpm  # noqa: E402
 import large_real_model as lrm  # noqa: E402
 
 from oracle import np_reference as ref  # noqa: E402
+from tests import addon_checks as ac  # noqa: E402
 from tests import large_real_inventory as rinv  # noqa: E402
-from tests import test_kernel_inventory as kinv  # noqa: E402
 
 HIPCC = "/opt/rocm/bin/hipcc"
 CSRC = os.path.join(ROOT, "smfft_amd", "csrc")
@@ -143,51 +143,31 @@ def test_committed_row_is_the_generators_output():
 
 
 # ---- ISA of what ships -------------------------------------------------------------------------------
-def _makefile_flags(n):
-    for line in open(os.path.join(CSRC, "Makefile")):
-        m = re.match(rf"LARGE_REAL_FLAGS_{n}\s*:=(.*)", line)
-        if m:
-            return m.group(1).split()
-    raise AssertionError(f"LARGE_REAL_FLAGS_{n} missing from the Makefile")
-
-
 @needs_hipcc
 @pytest.mark.parametrize("n", SIZES)
 def test_isa_budget(tmp_path, n):
-    out = tmp_path / f"large_real_{n}.s"
-    p = subprocess.run([HIPCC, "-O3", "--offload-arch=gfx950", "-std=c++17", "-fno-slp-vectorize", "-I" + os.path.join(ROOT, "include")]
-                       + _makefile_flags(n) + [f"-DSMFFT_LARGE_REAL_N={n}", "-S", "--cuda-device-only", os.path.join(CSRC, "smfft_large_real.hip"),
-                                               "-o", str(out)], capture_output=True, text=True)
-    assert p.returncode == 0, p.stderr[-2000:]
-    text = out.read_text()
-    kernels = re.findall(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", text, flags=re.S)
-    assert sorted(k for k, _ in kernels) == sorted([f"_ZN5smfft5large9large_c2rILi{n}EEEvPK15HIP_vector_typeIfLj2EEPfi",
+    text = ac.device_asm(os.path.join(CSRC, "smfft_large_real.hip"), ac.makefile_flags("LARGE_REAL", n) + [f"-DSMFFT_LARGE_REAL_N={n}"],
+                         tmp_path / f"large_real_{n}.s")
+    kernels = ac.descriptors(text)
+    assert sorted(kernels) == sorted([f"_ZN5smfft5large9large_c2rILi{n}EEEvPK15HIP_vector_typeIfLj2EEPfi",
                                                     f"_ZN5smfft5large9large_r2cILi{n}EEEvPKfP15HIP_vector_typeIfLj2EEi"])
-    for name, desc in kernels:
-        field = lambda key: int(re.search(rf"\.{key} (\d+)", desc).group(1))  # noqa: E731
-        assert field("amdhsa_private_segment_fixed_size") == 0, name
-        lds = field("amdhsa_group_segment_fixed_size")
+    for name in kernels:
+        assert ac.descriptor_field(kernels, name, "private_segment_fixed_size") == 0, name
+        lds = ac.descriptor_field(kernels, name, "group_segment_fixed_size")
         assert lds <= (81920 if n == 16384 else 163840), (name, lds)
-        assert field("amdhsa_next_free_vgpr") <= 128, name
+        assert ac.descriptor_field(kernels, name, "next_free_vgpr") <= 128, name
     assert not re.search(r"\bv_(sin|cos)_", text)
     assert not re.search(r"\bv_pk_(add|mul|fma)_f32", text)
     assert not re.search(r"\bscratch_", text)
 
 
 # ---- C ABI and Python mirror ---------------------------------------------------------------------------
-def _declared():
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "smfft_large_real.h")).read(), flags=re.S)
-    return dict(re.findall(r"\bint\s+(smfft_large_real_[a-z_]+)\s*\(([^)]*)\)", text))
-
-
 def test_python_mirror_matches_header(real_lib):
     from smfft_amd import large_real
-    decl = _declared()
+    decl = ac.declarations("smfft_large_real.h")
     assert sorted(decl) == sorted(large_real.SIGS) == ["smfft_large_real_benchmark", "smfft_large_real_grid", "smfft_large_real_launch"]
-    kinds = {"const void*": ctypes.c_void_p, "void*": ctypes.c_void_p, "int": ctypes.c_int, "double*": ctypes.POINTER(ctypes.c_double)}
-    for name, args in decl.items():
-        types = [kinds[re.sub(r"\s*\w+$", "", a.strip())] for a in args.split(",")]
-        assert large_real.SIGS[name] == (ctypes.c_int, types), name
+    for name, (res, args) in decl.items():
+        assert res == "int" and large_real.SIGS[name] == ac.signature(res, args), name
     assert large_real.SIZES == SIZES
     lib = ctypes.CDLL(real_lib)
     for name in decl:
@@ -229,17 +209,4 @@ def test_import_does_not_load_the_large_real_library():
 
 # ---- kernel inventory of libsmfft_large_real.so -----------------------------------------------------------
 def test_every_large_real_kernel_is_in_the_inventory_with_its_tests(real_lib):
-    handles, stubs = kinv._shipped_kernels(real_lib)
-    assert handles == stubs and len(handles) == 4, (sorted(handles), sorted(stubs))
-    assert handles == set(rinv.KERNELS), (sorted(handles ^ set(rinv.KERNELS)))
-    for name, entry in rinv.KERNELS.items():
-        assert set(entry) == {"call", "tests", "bounds", "probes", "host"}, name
-        assert entry["call"].startswith("smfft_large_real_"), name
-        for key in ("tests", "bounds", "probes", "host"):
-            assert entry[key], (name, key)
-            for tid in entry[key]:
-                m = re.fullmatch(r"(tests/test_\w+\.py)::(test_\w+)", tid)
-                assert m, tid
-                names, gpu = kinv._gpu_tests(os.path.join(ROOT, m.group(1)))
-                # "host": the run of the kernel on the host (tests/hostsim) belongs to the suite that needs no GPU
-                assert m.group(2) in names and gpu == (key != "host"), tid
+    ac.check_inventory(real_lib, rinv.KERNELS, "smfft_large_real_", 4)

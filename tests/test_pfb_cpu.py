@@ -18,12 +18,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import pfb_model as pm  # noqa: E402
 
+from tests import addon_checks as ac  # noqa: E402
+
 HIPCC = "/opt/rocm/bin/hipcc"
 CSRC = os.path.join(ROOT, "smfft_amd", "csrc")
 PFB_SRC = os.path.join(CSRC, "smfft_pfb.hip")
 SIZES = (256, 512, 1024, 2048, 4096)
-# the Makefile's HIPFLAGS for smfft_pfb_<N>.o (less -fPIC / -Wall, which change no device code); PFB_FLAGS_<N> are read from it
-FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fno-slp-vectorize", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC]
 needs_hipcc = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 VGPR_BUDGET = 168          # three waves per SIMD: the persistent grid of smfft_pfb.hip (kWorkgroupsPerCu) rests on it
 
@@ -187,29 +187,17 @@ def test_replay_stores_once_and_loads_inside_the_window(case):
 
 
 # ------------------------------------------------------------------------------------------------ gfx950 code
-def _makefile_flags(n):
-    text = open(os.path.join(CSRC, "Makefile")).read()
-    m = re.search(r"^PFB_FLAGS_%d\s*:=(.*)$" % n, text, re.M)
-    assert m, n
-    return m.group(1).split()
-
-
-def _compile(n):
-    out = f"/tmp/smfft_test_pfb_{os.getpid()}_{n}.s"
-    p = subprocess.run([HIPCC] + FLAGS + _makefile_flags(n) + [f"-DSMFFT_PFB_N={n}", "-S", "--cuda-device-only", PFB_SRC, "-o", out],
-                       capture_output=True, text=True)
-    assert p.returncode == 0, p.stderr[-2000:]
-    text = open(out).read()
-    os.remove(out)
-    return text
-
-
 @pytest.fixture(scope="module")
-def isa():
+def isa(tmp_path_factory):
+    """smfft_pfb_<N>.o as the Makefile compiles it: -I. and PFB_FLAGS_<N>"""
     if not os.path.exists(HIPCC):
         pytest.skip("hipcc not installed")
+    tmp = tmp_path_factory.mktemp("pfb_isa")
+
+    def compile_one(n):
+        return ac.device_asm(PFB_SRC, ["-I" + CSRC] + ac.makefile_flags("PFB", n) + [f"-DSMFFT_PFB_N={n}"], tmp / f"pfb_{n}.s")
     with concurrent.futures.ThreadPoolExecutor(len(SIZES)) as pool:
-        return dict(zip(SIZES, pool.map(_compile, SIZES)))
+        return dict(zip(SIZES, pool.map(compile_one, SIZES)))
 
 
 def _kernels(text):
@@ -220,11 +208,7 @@ def _kernels(text):
 
 
 def _descriptor(text, name, field):
-    d = re.search(r"\.amdhsa_kernel %s\n(.*?)\.end_amdhsa_kernel" % re.escape(name), text, re.S)
-    assert d, name
-    m = re.search(r"\.amdhsa_%s (\d+)" % field, d.group(1))
-    assert m, (name, field)
-    return int(m.group(1))
+    return ac.descriptor_field(ac.descriptors(text), name, field)
 
 
 def test_pfb_kernels_have_no_scratch_no_transcendentals_no_packed_f32(isa):
@@ -284,14 +268,10 @@ def test_header_declarations_equal_the_ctypes_signatures(pfb):
     header = open(os.path.join(ROOT, "include", "smfft_pfb.h")).read()
     for phrase in ("Out of scope", "oversampled", "real-valued input", "complex prototypes", "synthesis", "N <= 128", "N >= 8192"):
         assert phrase in header, phrase
-    code = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
-    decl = {m.group(2): (m.group(1), m.group(3)) for m in re.finditer(r"^(int|long long) (smfft_\w+)\(([^)]*)\);", code, re.M)}
+    decl = ac.declarations("smfft_pfb.h")
     assert sorted(decl) == sorted(pfb.SIGS) == sorted(NAMES)
-    kinds = {"const void*": ctypes.c_void_p, "void*": ctypes.c_void_p, "int": ctypes.c_int, "long long": ctypes.c_longlong,
-             "double*": ctypes.POINTER(ctypes.c_double)}
     for name, (res, args) in decl.items():
-        types = [kinds[re.sub(r"\s*\w+$", "", a.strip())] for a in args.split(",")]
-        assert pfb.SIGS[name] == (kinds[res], types), name
+        assert pfb.SIGS[name] == ac.signature(res, args), name
     # launch_tuned = the arguments of launch + tile_run; benchmark = launch with the timer in the stream's place
     assert pfb.SIGS["smfft_pfb_launch_tuned"][1] == pfb.SIGS["smfft_pfb_launch"][1] + [ctypes.c_int]
     assert pfb.SIGS["smfft_pfb_benchmark"][1][:-1] == pfb.SIGS["smfft_pfb_launch"][1][:-1]

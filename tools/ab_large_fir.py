@@ -71,15 +71,6 @@ def report(name, v, C, L, K, N, transforms):
     return med
 
 
-def load_ab(path):
-    from smfft_amd import large_fir
-    lib = ctypes.CDLL(path)
-    for name, (res, args) in large_fir.SIGS.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = res, args
-    return lib
-
-
 def main_config(torch, sm, large, lf, N, M, args, rng):
     stream = torch.cuda.current_stream()
     sp = stream.cuda_stream
@@ -135,7 +126,7 @@ def main_config(torch, sm, large, lf, N, M, args, rng):
     # once C S reaches the CU count), one per (segment, filter) in the recompute form
     fused_transforms = C * S * (1 + K) if N == 8192 else 2 * C * S * K
     transforms = {n: (fused_transforms if n.startswith("fused") else C * S * (1 + K)) for n in fns}
-    ab = load_ab(args.ab) if args.ab and N == 8192 else None
+    ab = lf.load(args.ab) if args.ab and N == 8192 else None
     if ab is not None:
         fns["recompute  (A/B build, hipMalloc output)"] = fused(plain, ab)
         transforms["recompute  (A/B build, hipMalloc output)"] = 2 * C * S * K

@@ -3,6 +3,9 @@
 
 Compiles, on a checkout of BASE (git archive into a temporary directory) and on the working tree, with the Makefile's flags:
   smfft_amd/csrc/smfft_inst.hip   both objects (SMFFT_INST_PART = 1, 2 with tools/inst_flags.py) of all 8 lengths
+  smfft_amd/csrc/smfft_large.hip, smfft_large_real.hip, smfft_large_fir.hip, smfft_pfb.hip
+                                  the per-length objects of the four add-on libraries, each with its <PREFIX>_FLAGS_<N> of the Makefile
+                                  (and the -I. of the two that include headers of that directory), where BASE has the file
   examples/*.hip                  the files BASE has
 to device assembly (hipcc -S --cuda-device-only) and compares every kernel BASE has, text of its body and its .amdhsa descriptor,
 with the basic-block labels (.LBB<f>_<n>) and the function-local symbols renumbered in order of appearance.
@@ -21,6 +24,18 @@ from inst_flags import part_flags  # noqa: E402
 HIPCC = "/opt/rocm/bin/hipcc"
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-fno-slp-vectorize", "-Wall", "-Wno-unused-function"]
 SIZES = (32, 64, 128, 256, 512, 1024, 2048, 4096)
+# the add-on libraries: source without .hip, the Makefile's prefix, its lengths, whether the Makefile compiles it with -I.
+ADDONS = (("smfft_large", "LARGE", (8192, 16384), False), ("smfft_large_real", "LARGE_REAL", (16384, 32768), False),
+          ("smfft_large_fir", "LARGE_FIR", (8192, 16384), True), ("smfft_pfb", "PFB", (256, 512, 1024, 2048, 4096), True))
+
+
+def addon_flags(prefix, n):
+    """the words of the line `<prefix>_FLAGS_<n> :=` of the working tree's Makefile"""
+    for line in open(os.path.join(ROOT, "smfft_amd", "csrc", "Makefile")):
+        m = re.match(rf"{prefix}_FLAGS_{n}\s*:=(.*)", line)
+        if m:
+            return m.group(1).split()
+    raise SystemExit(f"{prefix}_FLAGS_{n} missing from the Makefile")
 
 
 def units(tree):
@@ -28,6 +43,11 @@ def units(tree):
     for n in SIZES:
         for part in (1, 2):
             out.append((f"smfft_inst_{n}_part{part}", "smfft_amd/csrc/smfft_inst.hip", part_flags(n, part) + [f"-DSMFFT_N={n}"]))
+    for stem, prefix, sizes, local in ADDONS:
+        rel = f"smfft_amd/csrc/{stem}.hip"
+        if os.path.exists(os.path.join(tree, rel)):
+            for n in sizes:       # ("{tree}": compile_unit puts the tree it compiles there)
+                out.append((f"{stem}_{n}", rel, (["-I{tree}/smfft_amd/csrc"] if local else []) + addon_flags(prefix, n) + [f"-DSMFFT_{prefix}_N={n}"]))
     for ex in sorted(os.listdir(os.path.join(tree, "examples"))):
         if ex.endswith(".hip"):
             out.append((ex, "examples/" + ex, []))
@@ -35,7 +55,8 @@ def units(tree):
 
 
 def compile_unit(tree, rel, extra, dst):
-    cmd = [HIPCC] + FLAGS + ["-I" + os.path.join(tree, "include")] + extra + ["-S", "--cuda-device-only", os.path.join(tree, rel), "-o", dst]
+    cmd = [HIPCC] + FLAGS + ["-I" + os.path.join(tree, "include")] + [e.replace("{tree}", tree) for e in extra]
+    cmd += ["-S", "--cuda-device-only", os.path.join(tree, rel), "-o", dst]
     p = subprocess.run(cmd, capture_output=True, text=True)
     if p.returncode != 0:
         raise RuntimeError(p.stderr[-3000:])
