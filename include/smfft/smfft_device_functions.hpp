@@ -48,9 +48,10 @@ namespace smfft {
 // Hermitian split (forward, after the C2C) / merge (inverse, before the C2C) on the natural
 // layout in LDS; thread u of an FFT handles the 8 index pairs i = 1 + u + T*j, (i, L - i).
 // ------------------------------------------------------------------------------------------------
-template <int L, int DIR>
-__device__ __forceinline__ void hermitian_pass(float2* sf, int u) {
-    static_assert(L <= 2048, "R2C / C2R: complex length L = real length / 2 <= 2048 (the twiddle step 4096 / (2L) of the split / merge)");
+// hermitian_pass_with: the pass with the twiddles W_{2L}^i (forward sign, conjugated for DIR = 1) handed in as w_of(i), 1 <= i <= L/2
+// -- for callers whose 2L exceeds the 4096-entry table (smfft_pfb_real.hip: L = 4096).  hermitian_pass below is the table's form.
+template <int L, int DIR, class TwiddleOf>
+__device__ __forceinline__ void hermitian_pass_with(float2* sf, int u, TwiddleOf w_of) {
     constexpr int T = L / 16;
     constexpr float ohx = DIR ? -0.5f : 0.5f;   // upstream's (ohx, ohy) = (1/2, -1/2) forward, (-1/2, 1/2) inverse (RC:289-328)
     if (DIR) {
@@ -66,7 +67,7 @@ __device__ __forceinline__ void hermitian_pass(float2* sf, int u) {
     for (int j = 0; j < 8; ++j) {
         const int i = 1 + u + T * j;
         const float2 A = sf[i], B = sf[L - i];
-        const float2 W = twiddle<DIR>(i * (4096 / (2 * L)));
+        const float2 W = w_of(i);
         const float2 Wh = make_float2(ohx * W.x, ohx * W.y);
         const float2 S = make_float2(A.x + B.x, A.y - B.y);
         const float2 D = make_float2(A.y + B.y, A.x - B.x);
@@ -80,6 +81,12 @@ __device__ __forceinline__ void hermitian_pass(float2* sf, int u) {
             sf[0] = make_float2(z.x + z.y, z.x - z.y);
         }
     }
+}
+
+template <int L, int DIR>
+__device__ __forceinline__ void hermitian_pass(float2* sf, int u) {
+    static_assert(L <= 2048, "R2C / C2R: complex length L = real length / 2 <= 2048 (the twiddle step 4096 / (2L) of the split / merge)");
+    hermitian_pass_with<L, DIR>(sf, u, [](int i) { return twiddle<DIR>(i * (4096 / (2 * L))); });
 }
 
 // In place on LDS, natural layout (device-function form; RC:269-344).

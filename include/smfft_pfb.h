@@ -22,8 +22,9 @@
  * Return values: 0, a hipError_t, or -1 -- before any HIP call -- for an unsupported combination (n_channels, taps_per_channel,
  * n_streams <= 0, signal_length < 0, tile_run < 0).  F == 0 launches nothing and returns 0.
  *
- * Out of scope: oversampled banks (hop != N), real-valued input, complex prototypes, the synthesis (inverse) bank, N <= 128 (16 or
- * fewer threads per FFT would load 8 ... 64-byte pieces: that needs a staging path of its own, as for smfft_fir_*) and N >= 8192.
+ * Out of scope: oversampled banks (hop != N), real-valued input (that is smfft_pfb_real.h: libsmfft_pfb_real.so), complex prototypes,
+ * the synthesis (inverse) bank, N <= 128 (16 or fewer threads per FFT would load 8 ... 64-byte pieces: that needs a staging path of
+ * its own, as for smfft_fir_*) and N >= 8192.
  */
 #ifndef SMFFT_PFB_H_
 #define SMFFT_PFB_H_
