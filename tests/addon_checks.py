@@ -1,4 +1,5 @@
-"""What the CPU tests of the add-on libraries share (test_large_cpu.py, test_large_real_cpu.py, test_large_fir_cpu.py, test_pfb_cpu.py):
+"""What the CPU tests of the add-on libraries share (test_large_cpu.py, test_large_real_cpu.py, test_large_fir_cpu.py, test_pfb_cpu.py,
+test_pfb_real_cpu.py):
 the per-length flags of the Makefile, the compile of a per-length object to gfx950 assembly as the Makefile compiles it, the fields of
 a kernel descriptor, the declarations of a C header as ctypes signatures, and the walk through a kernel inventory."""
 import ctypes
@@ -56,17 +57,22 @@ def signature(res, args):
     return CTYPES[res], [CTYPES[re.sub(r"\s*\w+$", "", a.strip())] for a in args.split(",")]
 
 
-def check_inventory(lib_path, kernels, call_prefix, count):
-    """the library ships exactly the `count` kernels of the inventory `kernels`, and every entry names its C entry point and, per kind,
-    tests that exist: GPU tests, except "host", the run of the kernel on the host (tests/hostsim), which needs no GPU"""
+INVENTORY_KINDS = ("tests", "bounds", "probes", "host")
+
+
+def check_inventory(lib_path, kernels, call_prefix, count, kinds=INVENTORY_KINDS):
+    """the library ships exactly the `count` kernels of the inventory `kernels`, and every entry names its C entry point and, per kind
+    of `kinds`, tests that exist: GPU tests, except "host", the run of the kernel on the host (tests/hostsim), which needs no GPU.  An
+    inventory whose kernels hostsim cannot run passes kinds without "host" and says why in its docstring."""
     from tests import test_kernel_inventory as kinv
     handles, stubs = kinv._shipped_kernels(lib_path)
     assert handles == stubs and len(handles) == count, (sorted(handles), sorted(stubs))
     assert handles == set(kernels), (sorted(handles ^ set(kernels)))
+    assert set(kinds) <= set(INVENTORY_KINDS) and {"tests", "bounds", "probes"} <= set(kinds), kinds
     for name, entry in kernels.items():
-        assert set(entry) == {"call", "tests", "bounds", "probes", "host"}, name
+        assert set(entry) == {"call"} | set(kinds), name
         assert entry["call"].startswith(call_prefix), name
-        for key in ("tests", "bounds", "probes", "host"):
+        for key in kinds:
             assert entry[key], (name, key)
             for tid in entry[key]:
                 m = re.fullmatch(r"(tests/test_\w+\.py)::(test_\w+)", tid)

@@ -2,7 +2,7 @@
 two forms of the definition agree, the header's PfbPlan compiled for the host gives the model's frames, tiles, offsets and schedule,
 the replay of the kernel's loop stores every output once and loads inside its own stream's window, the gfx950 code keeps the
 library's rules (no scratch, no v_sin / v_cos, no packed f32, the sixteen signal loads of a tap together), the C ABI declares, exports
-and validates without a device, and the leakage property the GPU test relies on holds for the model.  No GPU code is run (hipcc
+and validates without a device, every shipped kernel is in tests/pfb_inventory.py with its tests, and the leakage property the GPU test relies on holds for the model.  No GPU code is run (hipcc
 cross-compiles gfx950)."""
 import concurrent.futures
 import ctypes
@@ -19,6 +19,7 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 import pfb_model as pm  # noqa: E402
 
 from tests import addon_checks as ac  # noqa: E402
+from tests import pfb_inventory as pinv  # noqa: E402
 
 HIPCC = "/opt/rocm/bin/hipcc"
 CSRC = os.path.join(ROOT, "smfft_amd", "csrc")
@@ -343,6 +344,12 @@ def test_prototype(pfb):
     assert np.array_equal(pfb.prototype(256, 2, "rectangular"), np.sinc((np.arange(512) - 255.5) / 256).astype(np.float32))
     with pytest.raises(ValueError):
         pfb.prototype(256, 2, "kaiser")
+
+
+# ------------------------------------------------------------------------------------------------ kernel inventory
+def test_every_pfb_kernel_is_in_the_inventory_with_its_tests(pfb):
+    """the rule of tests/test_kernel_inventory.py, without the "host" kind (tests/pfb_inventory.py says why)"""
+    ac.check_inventory(pfb.LIB_PATH, pinv.KERNELS, "smfft_pfb_", 10, kinds=("tests", "bounds", "probes"))
 
 
 # ------------------------------------------------------------------------------------------------ leakage

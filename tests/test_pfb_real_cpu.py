@@ -1,7 +1,7 @@
 """The polyphase filter bank channelizer for real streams (smfft_amd/csrc/smfft_pfb_real.hip, include/smfft_pfb_real.h) on the CPU: the
 fp64 model's two forms of the definition agree, with one tap of ones it is np.fft.rfft, and it equals channels 0 ... N of the complex
 bank's model at 2N channels; the gfx950 code keeps the library's rules (no scratch, no v_sin / v_cos, no packed f32, the VGPRs of three
-workgroups per compute unit, the sixteen signal loads of a tap together); the C ABI declares, exports and validates without a device.
+workgroups per compute unit, the sixteen signal loads of a tap together); the C ABI declares, exports and validates without a device; every shipped kernel is in tests/pfb_inventory.py with its tests.
 No GPU code is run (hipcc cross-compiles gfx950)."""
 import concurrent.futures
 import ctypes
@@ -19,6 +19,7 @@ import pfb_model as pm  # noqa: E402
 import pfb_real_model as prm  # noqa: E402
 
 from tests import addon_checks as ac  # noqa: E402
+from tests import pfb_inventory as pinv  # noqa: E402
 
 HIPCC = "/opt/rocm/bin/hipcc"
 CSRC = os.path.join(ROOT, "smfft_amd", "csrc")
@@ -211,6 +212,11 @@ def test_unsupported_combinations_return_minus_one_without_a_device(pr):
     assert pr.channelize(np.zeros((2, 1000), np.float32), np.zeros(1024, np.float32), 256).shape == (2, 0, 257)
     assert pr.channelize(np.zeros((2, 1000), np.float32), np.zeros(1024, np.float32), 256, packed=True).shape == (2, 0, 256)
     assert pr.channelize(np.zeros((2, 1000), np.float32), np.zeros(1024, np.float32), 256, power=True).shape == (2, 0, 256)
+
+
+def test_every_pfb_real_kernel_is_in_the_inventory_with_its_tests(pr):
+    """the rule of tests/test_kernel_inventory.py, without the "host" kind (tests/pfb_inventory.py says why)"""
+    ac.check_inventory(pr.LIB_PATH, pinv.REAL_KERNELS, "smfft_pfb_real_", 10, kinds=("tests", "bounds", "probes"))
 
 
 def test_frames_over_ragged_lengths_and_default_tile_run(pr):
