@@ -1,0 +1,110 @@
+"""What the ctypes mirrors of the two polyphase filter banks share (smfft_amd.pfb: complex streams, smfft_amd.pfb_real: real streams):
+the five entry points' signatures, the calls with their error messages, the prototype and the host-array round trip.  The libraries'
+C ABIs are one for one the same; a bank differs by its prefix, by the samples a frame takes per channel (1: N complex samples, 2: 2N
+real samples) and by the signal's dtype.  The public functions, with the documentation of what each bank computes, are the mirrors'."""
+import ctypes
+
+import numpy as np
+
+SIZES = (256, 512, 1024, 2048, 4096)
+MAX_TAPS_PER_CHANNEL = 32
+
+_vp, _i, _ll, _dp = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.POINTER(ctypes.c_double)
+
+
+def sigs(prefix):
+    """name -> (restype, argtypes) of the five functions of include/<prefix>.h"""
+    return {
+        prefix + "_frames": (_ll, [_ll, _i, _i]),
+        prefix + "_launch": (_i, [_vp, _ll, _i, _vp, _i, _i, _i, _vp, _vp]),
+        prefix + "_benchmark": (_i, [_vp, _ll, _i, _vp, _i, _i, _i, _vp, _dp]),
+        prefix + "_launch_tuned": (_i, [_vp, _ll, _i, _vp, _i, _i, _i, _vp, _vp, _i]),
+        prefix + "_default_tile_run": (_i, [_i, _i]),
+    }
+
+
+class Bank:
+    def __init__(self, name, prefix, lib, real):
+        """name: the mirror's, for messages ("pfb"); prefix: of its C functions ("smfft_pfb"); lib: the mirror's lib(); real: real streams"""
+        self.name, self.prefix, self.lib, self.real = name, prefix, lib, real
+        self.per_channel = 2 if real else 1           # samples of a frame per channel: a frame is `per_channel * N` samples
+        self.chunk = "2N" if real else "N"
+
+    def call(self, function, *args):
+        return getattr(self.lib(), f"{self.prefix}_{function}")(*args)
+
+    def frames(self, L, N, P):
+        f = self.call("frames", L, N, P)
+        if f < 0:
+            raise ValueError(f"{self.prefix}_frames(L={L}, N={N}, P={P}) -> {f}: N must be one of {SIZES}, "
+                             f"1 <= P <= {MAX_TAPS_PER_CHANNEL}, L >= 0" + (" and even" if self.real else ""))
+        return f
+
+    def default_tile_run(self, N, P):
+        r = self.call("default_tile_run", N, P)
+        if r < 0:
+            raise ValueError(f"{self.prefix}_default_tile_run(N={N}, P={P}) -> {r}")
+        return r
+
+    def launch(self, d_signal, L, C, d_taps, N, P, d_output, power, stream):
+        rc = self.call("launch", d_signal, L, C, d_taps, N, P, int(bool(power)), d_output, stream)
+        if rc != 0:
+            raise RuntimeError(f"{self.prefix}_launch(L={L}, C={C}, N={N}, P={P}) -> {rc}")
+
+    def launch_tuned(self, d_signal, L, C, d_taps, N, P, d_output, tile_run, power, stream):
+        rc = self.call("launch_tuned", d_signal, L, C, d_taps, N, P, int(bool(power)), d_output, stream, tile_run)
+        if rc != 0:
+            raise RuntimeError(f"{self.prefix}_launch_tuned(L={L}, C={C}, N={N}, P={P}, R={tile_run}) -> {rc}")
+
+    def benchmark(self, d_signal, L, C, d_taps, N, P, d_output, power):
+        t = ctypes.c_double(0.0)
+        rc = self.call("benchmark", d_signal, L, C, d_taps, N, P, int(bool(power)), d_output, ctypes.byref(t))
+        return rc, t.value
+
+    def prototype(self, n_channels, taps_per_channel, window):
+        N, P = int(n_channels), int(taps_per_channel)
+        if N < 1 or P < 1:
+            raise ValueError(f"prototype(N={N}, P={P})")
+        M = self.per_channel * P * N
+        if window == "rectangular":
+            w = np.ones(M)
+        elif window in ("hamming", "hanning", "blackman", "bartlett"):
+            w = getattr(np, window)(M)
+        else:
+            raise ValueError(f"unknown window {window!r}")
+        m = np.arange(M, dtype=np.float64)
+        return (np.sinc((m - (M - 1) / 2) / (self.per_channel * N)) * w).astype(np.float32)
+
+    def channelize(self, x, taps, n_channels, power):
+        """host arrays -> the (C, F, N) rows as the device writes them"""
+        x, taps = np.asarray(x), np.asarray(taps)
+        if x.ndim not in (1, 2) or taps.ndim != 1:
+            raise ValueError(f"x must be (C, L) or (L,), taps a vector of P {self.chunk} coefficients")
+        if np.iscomplexobj(taps) or (self.real and np.iscomplexobj(x)):
+            raise ValueError("the signal and the prototype must be real (complex signals: smfft_amd.pfb)" if self.real else "the prototype must be real")
+        N = int(n_channels)
+        frame = self.per_channel * N
+        if N not in SIZES or taps.size % frame or not 1 <= taps.size // frame <= MAX_TAPS_PER_CHANNEL:
+            raise ValueError(f"smfft_amd.{self.name} serves N in {SIZES} with P {self.chunk} taps, 1 <= P <= {MAX_TAPS_PER_CHANNEL}, "
+                             f"not N = {N} with {taps.size} taps")
+        P = taps.size // frame
+        x = np.ascontiguousarray(np.atleast_2d(x), dtype=np.float32 if self.real else np.complex64)
+        taps = np.ascontiguousarray(taps, dtype=np.float32)
+        C, L = x.shape
+        F = self.frames(L, N, P)
+        dtype, width = (np.float32, 4) if power else (np.complex64, 8)
+        if C * F == 0:
+            return np.empty((C, F, N), dtype)
+        from . import api      # the device allocator and copies of libsmfft_amd.so
+        din, dtaps = api.DeviceBuffer.from_host(x), api.DeviceBuffer.from_host(taps)
+        dout = api.DeviceBuffer(C * F * N * width)
+        api.lib.smfft_memset(dout.ptr, 0xFF, dout.nbytes)   # NaN pattern: untouched outputs are caught
+        rc = self.call("launch", din.ptr, L, C, dtaps.ptr, N, P, int(bool(power)), dout.ptr, None)
+        if rc == 0:
+            rc = api.lib.smfft_synchronize()
+        if rc != 0:
+            raise RuntimeError(f"{self.name}.channelize(C={C}, L={L}, N={N}, P={P}) -> {rc}")
+        out = dout.to_host(dtype, (C, F, N))
+        for b in (din, dtaps, dout):
+            b.free()
+        return out

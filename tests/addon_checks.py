@@ -79,3 +79,131 @@ def check_inventory(lib_path, kernels, call_prefix, count, kinds=INVENTORY_KINDS
                 assert m, tid
                 names, gpu = kinv._gpu_tests(os.path.join(ROOT, m.group(1)))
                 assert m.group(2) in names and gpu == (key != "host"), tid
+
+
+# ------------------------------------------------------------------------------------------------ the two polyphase filter banks
+# What test_pfb_cpu.py and test_pfb_real_cpu.py hold both banks to.  A bank is named by its source stem ("smfft_pfb"), which is also the
+# prefix of its C functions, its Makefile prefix ("PFB") and its kernel ("pfb_kernel").
+PFB_SIZES = (256, 512, 1024, 2048, 4096)
+PFB_KERNEL_HEADER = os.path.join(CSRC, "smfft_pfb_kernel.hpp")      # the one kernel body and its kWorkgroupsPerCu
+PFB_WORKGROUPS_PER_CU = 3
+PFB_VGPR_BUDGET = 168          # three waves per SIMD: 512 registers / 3, in granules of 8; the persistent grid rests on it
+LDS_PER_CU = 160 * 1024
+
+
+def pfb_isa(stem, prefix, tmp):
+    """{N: gfx950 assembly of <stem>_<N>.o as the Makefile compiles it: -I. and <prefix>_FLAGS_<N>}"""
+    import concurrent.futures
+
+    def compile_one(n):
+        return device_asm(os.path.join(CSRC, stem + ".hip"), ["-I" + CSRC] + makefile_flags(prefix, n) + [f"-DSMFFT_{prefix}_N={n}"], tmp / f"{stem}_{n}.s")
+    with concurrent.futures.ThreadPoolExecutor(len(PFB_SIZES)) as pool:
+        return dict(zip(PFB_SIZES, pool.map(compile_one, PFB_SIZES)))
+
+
+def pfb_kernels(text, kernel):
+    """{mangled name: the stripped lines of its body} of the instantiations of `kernel` in an assembly text"""
+    found = {}
+    for m in re.finditer(r"^(_Z\w*%s\w*):[^\n]*\n(.*?)\n\s*s_endpgm" % kernel, text, re.S | re.M):
+        found[m.group(1)] = [line.strip() for line in m.group(2).split("\n")]
+    return found
+
+
+def check_pfb_kernel_rules(isa, kernel):
+    """two kernels per length and nothing else, ten in all: no scratch, no v_sin / v_cos, no packed f32, the LDS of 4096 points and the
+    VGPRs of three workgroups per compute unit, the figure the shared kernel header launches the persistent grid with"""
+    assert re.search(r"constexpr int kWorkgroupsPerCu = %d;" % PFB_WORKGROUPS_PER_CU, open(PFB_KERNEL_HEADER).read())
+    total = 0
+    for n, text in isa.items():
+        kernels, descs = pfb_kernels(text, kernel), descriptors(text)
+        assert len(kernels) == 2 and len(descs) == 2, (n, sorted(kernels), sorted(descs))          # complex and power, nothing else
+        total += len(kernels)
+        for name, body in kernels.items():
+            assert "%sILi%dE" % (kernel, n) in name
+            assert not [line for line in body if line.startswith("scratch_")], name
+            assert not [line for line in body if re.match(r"v_(sin|cos)_", line)], name
+            assert not [line for line in body if re.match(r"v_pk_\w+_f32", line)], name
+            assert descriptor_field(descs, name, "private_segment_fixed_size") == 0, name
+            vgprs, lds = descriptor_field(descs, name, "next_free_vgpr"), descriptor_field(descs, name, "group_segment_fixed_size")
+            print(f"N={n:5d} {'power  ' if 'ELi1EEE' in name else 'complex'}: {vgprs} VGPRs, {lds} B of LDS")
+            assert lds == 4096 // 16 * 17 * 8 and PFB_WORKGROUPS_PER_CU * lds <= LDS_PER_CU, name
+            assert vgprs <= PFB_VGPR_BUDGET, (name, vgprs)
+    assert total == 10
+
+
+def check_pfb_signal_loads(isa, kernel, signal, tap, arithmetic):
+    """the sixteen signal loads of one tap (lines matching `signal`; the kernel's only non-temporal loads) are contiguous in the
+    instruction stream up to address arithmetic (lines matching `arithmetic`), with no branch, barrier or vmcnt(0) between the first and
+    the last, and sit in a loop (a backward branch follows them); its sixteen coefficient loads (lines matching `tap`) follow them
+    inside the loop"""
+    for n, text in isa.items():
+        for name, body in pfb_kernels(text, kernel).items():
+            loads = [i for i, line in enumerate(body) if re.match(signal, line)]
+            assert len(loads) == 16, (name, len(loads))
+            assert len([line for line in body if line.startswith("global_load") and line.endswith(" nt")]) == 16, name
+            between = body[loads[0]:loads[-1] + 1]
+            assert not [line for line in between if line.startswith(("s_cbranch", "s_branch", "s_setpc", "s_barrier"))], name
+            assert not [line for line in between if re.search(r"vmcnt\(0\)", line)], name
+            others = [line for line in between if line and not line.startswith("global_load_dwordx2")]
+            assert all(re.match(arithmetic, line) for line in others), (name, others)
+            # the loop: the first label before the loads is the target of the first branch after them
+            label = next(line for line in reversed(body[:loads[0]]) if re.match(r"\.LBB\d+_\d+:", line)).split(":")[0]
+            branch = next(line for line in body[loads[-1]:] if line.startswith("s_cbranch"))
+            assert branch.split()[-1] == label, (name, label, branch)
+            end = body.index(branch, loads[-1])
+            taps = [i for i in range(loads[-1] + 1, end) if re.match(tap, body[i])]
+            assert len(taps) == 16, (name, len(taps))
+
+
+def pfb_names(stem):
+    return tuple(f"{stem}_{f}" for f in ("frames", "launch", "benchmark", "launch_tuned", "default_tile_run"))
+
+
+def check_pfb_declarations(mirror, stem, phrases):
+    """include/<stem>.h says what is out of scope (`phrases`) and declares exactly the five functions of the mirror's SIGS"""
+    header = open(os.path.join(ROOT, "include", stem + ".h")).read()
+    for phrase in phrases:
+        assert phrase in header, phrase
+    decl = declarations(stem + ".h")
+    assert sorted(decl) == sorted(mirror.SIGS) == sorted(pfb_names(stem))
+    for name, (res, args) in decl.items():
+        assert mirror.SIGS[name] == signature(res, args), name
+    # launch_tuned = the arguments of launch + tile_run; benchmark = launch with the timer in the stream's place
+    assert mirror.SIGS[stem + "_launch_tuned"][1] == mirror.SIGS[stem + "_launch"][1] + [ctypes.c_int]
+    assert mirror.SIGS[stem + "_benchmark"][1][:-1] == mirror.SIGS[stem + "_launch"][1][:-1]
+    assert mirror.SIZES == PFB_SIZES
+
+
+def check_pfb_exports(mirror, stem):
+    nm = subprocess.run(["nm", "-D", "--defined-only", mirror.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    assert sorted(re.findall(r" T (smfft_\w+)$", nm, re.M)) == sorted(pfb_names(stem))
+
+
+def check_pfb_rejections(mirror, stem, samples, bad_lengths):
+    """all validation happens before any HIP call: these return -1 (or 0 when there is no whole frame) with no device and null pointers.
+    samples: of the signal per channel of a frame (1 complex, 2 real); bad_lengths: (L, C, N, P) with a signal length the bank refuses
+    at a supported shape"""
+    lib = mirror.lib()
+    frames, launch, benchmark, launch_tuned, default_tile_run = (getattr(lib, name) for name in pfb_names(stem))
+    t = ctypes.c_double(0.0)
+    bad = [(1 << 20, 1, n, 4) for n in (0, 128, 1000, 8192, -1024)] + [(1 << 20, 1, 1024, p) for p in (0, 33, -1)]
+    bad += [(1 << 20, c, 1024, 4) for c in (0, -1)] + list(bad_lengths)
+    for L, C, N, P in bad:
+        for power in (0, 1):
+            assert launch(None, L, C, None, N, P, power, None, None) == -1, (L, C, N, P)
+            assert launch_tuned(None, L, C, None, N, P, power, None, None, 3) == -1, (L, C, N, P)
+            assert benchmark(None, L, C, None, N, P, power, None, ctypes.byref(t)) == -1, (L, C, N, P)
+    assert launch_tuned(None, 1 << 20, 1, None, 1024, 4, 0, None, None, -1) == -1
+    # no whole frame is not an error: nothing is launched
+    for L in (0, samples * 1023, samples * (4 * 1024 - 1)):
+        for power in (0, 1):
+            assert launch(None, L, 2, None, 1024, 4, power, None, None) == 0
+            assert launch_tuned(None, L, 2, None, 1024, 4, power, None, None, 7) == 0
+            assert benchmark(None, L, 2, None, 1024, 4, power, None, ctypes.byref(t)) == 0
+    assert t.value == 0.0
+    for n in (0, 128, 1000, 8192):
+        assert frames(1 << 20, n, 4) == -1 and default_tile_run(n, 4) == -1
+    for p in (0, 33, -1):
+        assert frames(1 << 20, 1024, p) == -1 and default_tile_run(1024, p) == -1
+    for L, _, N, P in bad_lengths:
+        assert frames(L, N, P) == -1, (L, N, P)

@@ -4,8 +4,6 @@ the replay of the kernel's loop stores every output once and loads inside its ow
 library's rules (no scratch, no v_sin / v_cos, no packed f32, the sixteen signal loads of a tap together), the C ABI declares, exports
 and validates without a device, every shipped kernel is in tests/pfb_inventory.py with its tests, and the leakage property the GPU test relies on holds for the model.  No GPU code is run (hipcc
 cross-compiles gfx950)."""
-import concurrent.futures
-import ctypes
 import os
 import re
 import subprocess
@@ -23,10 +21,8 @@ from tests import pfb_inventory as pinv  # noqa: E402
 
 HIPCC = "/opt/rocm/bin/hipcc"
 CSRC = os.path.join(ROOT, "smfft_amd", "csrc")
-PFB_SRC = os.path.join(CSRC, "smfft_pfb.hip")
 SIZES = (256, 512, 1024, 2048, 4096)
 needs_hipcc = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
-VGPR_BUDGET = 168          # three waves per SIMD: the persistent grid of smfft_pfb.hip (kWorkgroupsPerCu) rests on it
 
 
 def _rand(rng, shape):
@@ -190,74 +186,23 @@ def test_replay_stores_once_and_loads_inside_the_window(case):
 # ------------------------------------------------------------------------------------------------ gfx950 code
 @pytest.fixture(scope="module")
 def isa(tmp_path_factory):
-    """smfft_pfb_<N>.o as the Makefile compiles it: -I. and PFB_FLAGS_<N>"""
     if not os.path.exists(HIPCC):
         pytest.skip("hipcc not installed")
-    tmp = tmp_path_factory.mktemp("pfb_isa")
-
-    def compile_one(n):
-        return ac.device_asm(PFB_SRC, ["-I" + CSRC] + ac.makefile_flags("PFB", n) + [f"-DSMFFT_PFB_N={n}"], tmp / f"pfb_{n}.s")
-    with concurrent.futures.ThreadPoolExecutor(len(SIZES)) as pool:
-        return dict(zip(SIZES, pool.map(compile_one, SIZES)))
-
-
-def _kernels(text):
-    found = {}
-    for m in re.finditer(r"^(_Z\w*pfb_kernel\w*):[^\n]*\n(.*?)\n\s*s_endpgm", text, re.S | re.M):
-        found[m.group(1)] = [line.strip() for line in m.group(2).split("\n")]
-    return found
-
-
-def _descriptor(text, name, field):
-    return ac.descriptor_field(ac.descriptors(text), name, field)
+    return ac.pfb_isa("smfft_pfb", "PFB", tmp_path_factory.mktemp("pfb_isa"))
 
 
 def test_pfb_kernels_have_no_scratch_no_transcendentals_no_packed_f32(isa):
-    total = 0
-    for n, text in isa.items():
-        kernels = _kernels(text)
-        assert len(kernels) == 2, (n, sorted(kernels))          # complex and power
-        total += len(kernels)
-        for name, body in kernels.items():
-            assert "pfb_kernelILi%dE" % n in name
-            assert not [line for line in body if line.startswith("scratch_")], name
-            assert not [line for line in body if re.match(r"v_(sin|cos)_", line)], name
-            assert not [line for line in body if re.match(r"v_pk_\w+_f32", line)], name
-            assert _descriptor(text, name, "private_segment_fixed_size") == 0, name
-            vgprs, lds = _descriptor(text, name, "next_free_vgpr"), _descriptor(text, name, "group_segment_fixed_size")
-            print(f"N={n:5d} {'power  ' if 'ELi1EEE' in name else 'complex'}: {vgprs} VGPRs, {lds} B of LDS")
-            assert lds == 4096 // 16 * 17 * 8, name
-            assert vgprs <= VGPR_BUDGET, (name, vgprs)
-    assert total == 10
+    ac.check_pfb_kernel_rules(isa, "pfb_kernel")
 
 
 def test_pfb_signal_loads_of_a_tap_are_issued_together(isa):
-    """the sixteen signal loads of one tap (the kernel's only 8-byte global loads through a vector address: the twiddle tables are
-    read through scalar bases, the coefficients are 4-byte loads) are contiguous in the instruction stream up to address arithmetic,
-    with no branch, barrier or vmcnt(0) between the first and the last, and sit in a loop (a backward branch follows them)"""
-    arithmetic = re.compile(r"(v_add|v_addc|v_lshl|v_lshlrev|v_mov|v_mad|v_ashr|v_and|v_or|s_add|s_addc|s_lshl|s_mov|s_nop|s_mul|;)")
-    for n, text in isa.items():
-        for name, body in _kernels(text).items():
-            loads = [i for i, line in enumerate(body) if re.match(r"global_load_dwordx2 v\[\d+:\d+\], v\[\d+:\d+\], off", line)]
-            assert len(loads) == 16, (name, len(loads))
-            between = body[loads[0]:loads[-1] + 1]
-            assert not [line for line in between if line.startswith(("s_cbranch", "s_branch", "s_setpc", "s_barrier"))], name
-            assert not [line for line in between if re.search(r"vmcnt\(0\)", line)], name
-            others = [line for line in between if line and not line.startswith("global_load_dwordx2")]
-            assert all(arithmetic.match(line) for line in others), (name, others)
-            # the loop: the first label before the loads is the target of the first branch after them
-            label = next(line for line in reversed(body[:loads[0]]) if re.match(r"\.LBB\d+_\d+:", line)).split(":")[0]
-            branch = next(line for line in body[loads[-1]:] if line.startswith("s_cbranch"))
-            assert branch.split()[-1] == label, (name, label, branch)
-            # its coefficient loads follow the signal loads
-            taps = [i for i, line in enumerate(body) if line.startswith("global_load_dword ") and loads[-1] < i]
-            assert len([i for i in taps if i < body.index(branch, loads[-1])]) == 16, name
+    """the signal loads are the kernel's only 8-byte global loads through a vector address: the twiddle tables are read through scalar
+    bases, the coefficients are 4-byte loads"""
+    ac.check_pfb_signal_loads(isa, "pfb_kernel", signal=r"global_load_dwordx2 v\[\d+:\d+\], v\[\d+:\d+\], off", tap=r"global_load_dword ",
+                              arithmetic=r"(v_add|v_addc|v_lshl|v_lshlrev|v_mov|v_mad|v_ashr|v_and|v_or|s_add|s_addc|s_lshl|s_mov|s_nop|s_mul|;)")
 
 
 # ------------------------------------------------------------------------------------------------ C ABI
-NAMES = ("smfft_pfb_frames", "smfft_pfb_launch", "smfft_pfb_benchmark", "smfft_pfb_launch_tuned", "smfft_pfb_default_tile_run")
-
-
 @pytest.fixture(scope="module")
 def pfb():
     from smfft_amd import pfb
@@ -266,22 +211,12 @@ def pfb():
 
 
 def test_header_declarations_equal_the_ctypes_signatures(pfb):
-    header = open(os.path.join(ROOT, "include", "smfft_pfb.h")).read()
-    for phrase in ("Out of scope", "oversampled", "real-valued input", "complex prototypes", "synthesis", "N <= 128", "N >= 8192"):
-        assert phrase in header, phrase
-    decl = ac.declarations("smfft_pfb.h")
-    assert sorted(decl) == sorted(pfb.SIGS) == sorted(NAMES)
-    for name, (res, args) in decl.items():
-        assert pfb.SIGS[name] == ac.signature(res, args), name
-    # launch_tuned = the arguments of launch + tile_run; benchmark = launch with the timer in the stream's place
-    assert pfb.SIGS["smfft_pfb_launch_tuned"][1] == pfb.SIGS["smfft_pfb_launch"][1] + [ctypes.c_int]
-    assert pfb.SIGS["smfft_pfb_benchmark"][1][:-1] == pfb.SIGS["smfft_pfb_launch"][1][:-1]
+    ac.check_pfb_declarations(pfb, "smfft_pfb", ("Out of scope", "oversampled", "real-valued input", "complex prototypes", "synthesis", "N <= 128", "N >= 8192"))
     assert pfb.SIZES == SIZES
 
 
 def test_library_exports_exactly_the_five_symbols(pfb):
-    nm = subprocess.run(["nm", "-D", "--defined-only", pfb.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert sorted(re.findall(r" T (smfft_\w+)$", nm, re.M)) == sorted(NAMES)
+    ac.check_pfb_exports(pfb, "smfft_pfb")
     # and libsmfft_amd.so keeps its list: nothing of the filter bank went into it
     import smfft_amd
     nm = subprocess.run(["nm", "-D", "--defined-only", smfft_amd.LIB_PATH], capture_output=True, text=True, check=True).stdout
@@ -289,29 +224,7 @@ def test_library_exports_exactly_the_five_symbols(pfb):
 
 
 def test_unsupported_combinations_return_minus_one_without_a_device(pfb):
-    """all validation happens before any HIP call: these return -1 (or 0 when there is no whole frame) with no device and null pointers"""
-    lib = pfb.lib()
-    t = ctypes.c_double(0.0)
-    bad = [(1 << 20, 1, n, 4) for n in (0, 128, 1000, 8192, -1024)] + [(1 << 20, 1, 1024, p) for p in (0, 33, -1)]
-    bad += [(1 << 20, c, 1024, 4) for c in (0, -1)] + [(-1, 1, 1024, 4)]
-    for L, C, N, P in bad:
-        for power in (0, 1):
-            assert lib.smfft_pfb_launch(None, L, C, None, N, P, power, None, None) == -1, (L, C, N, P)
-            assert lib.smfft_pfb_launch_tuned(None, L, C, None, N, P, power, None, None, 3) == -1, (L, C, N, P)
-            assert lib.smfft_pfb_benchmark(None, L, C, None, N, P, power, None, ctypes.byref(t)) == -1, (L, C, N, P)
-    assert lib.smfft_pfb_launch_tuned(None, 1 << 20, 1, None, 1024, 4, 0, None, None, -1) == -1
-    # no whole frame is not an error: nothing is launched
-    for L in (0, 1023, 4 * 1024 - 1):
-        for power in (0, 1):
-            assert lib.smfft_pfb_launch(None, L, 2, None, 1024, 4, power, None, None) == 0
-            assert lib.smfft_pfb_launch_tuned(None, L, 2, None, 1024, 4, power, None, None, 7) == 0
-            assert lib.smfft_pfb_benchmark(None, L, 2, None, 1024, 4, power, None, ctypes.byref(t)) == 0
-    assert t.value == 0.0
-    for n in (0, 128, 1000, 8192):
-        assert lib.smfft_pfb_frames(1 << 20, n, 4) == -1 and lib.smfft_pfb_default_tile_run(n, 4) == -1
-    for p in (0, 33, -1):
-        assert lib.smfft_pfb_frames(1 << 20, 1024, p) == -1 and lib.smfft_pfb_default_tile_run(1024, p) == -1
-    assert lib.smfft_pfb_frames(-1, 1024, 4) == -1
+    ac.check_pfb_rejections(pfb, "smfft_pfb", samples=1, bad_lengths=[(-1, 1, 1024, 4)])
     with pytest.raises(ValueError):
         pfb.frames(1000, 100, 4)
     with pytest.raises(RuntimeError):

@@ -3,11 +3,7 @@ fp64 model's two forms of the definition agree, with one tap of ones it is np.ff
 bank's model at 2N channels; the gfx950 code keeps the library's rules (no scratch, no v_sin / v_cos, no packed f32, the VGPRs of three
 workgroups per compute unit, the sixteen signal loads of a tap together); the C ABI declares, exports and validates without a device; every shipped kernel is in tests/pfb_inventory.py with its tests.
 No GPU code is run (hipcc cross-compiles gfx950)."""
-import concurrent.futures
-import ctypes
 import os
-import re
-import subprocess
 import sys
 
 import numpy as np
@@ -22,12 +18,7 @@ from tests import addon_checks as ac  # noqa: E402
 from tests import pfb_inventory as pinv  # noqa: E402
 
 HIPCC = "/opt/rocm/bin/hipcc"
-CSRC = os.path.join(ROOT, "smfft_amd", "csrc")
-SRC = os.path.join(CSRC, "smfft_pfb_real.hip")
 SIZES = (256, 512, 1024, 2048, 4096)
-WORKGROUPS_PER_CU = 3      # kWorkgroupsPerCu of smfft_pfb_real.hip
-VGPR_BUDGET = 168          # three waves per SIMD: 512 registers / 3, in granules of 8
-LDS_PER_CU = 160 * 1024
 
 
 # ------------------------------------------------------------------------------------------------ the model
@@ -76,75 +67,23 @@ def test_model_is_the_lower_half_of_the_complex_banks_model(N):
 # ------------------------------------------------------------------------------------------------ gfx950 code
 @pytest.fixture(scope="module")
 def isa(tmp_path_factory):
-    """smfft_pfb_real_<N>.o as the Makefile compiles it: -I. and PFB_REAL_FLAGS_<N>"""
     if not os.path.exists(HIPCC):
         pytest.skip("hipcc not installed")
-    tmp = tmp_path_factory.mktemp("pfb_real_isa")
-
-    def compile_one(n):
-        return ac.device_asm(SRC, ["-I" + CSRC] + ac.makefile_flags("PFB_REAL", n) + [f"-DSMFFT_PFB_REAL_N={n}"], tmp / f"pfb_real_{n}.s")
-    with concurrent.futures.ThreadPoolExecutor(len(SIZES)) as pool:
-        return dict(zip(SIZES, pool.map(compile_one, SIZES)))
-
-
-def _kernels(text):
-    found = {}
-    for m in re.finditer(r"^(_Z\w*pfb_real_kernel\w*):[^\n]*\n(.*?)\n\s*s_endpgm", text, re.S | re.M):
-        found[m.group(1)] = [line.strip() for line in m.group(2).split("\n")]
-    return found
+    return ac.pfb_isa("smfft_pfb_real", "PFB_REAL", tmp_path_factory.mktemp("pfb_real_isa"))
 
 
 def test_kernels_fit_three_workgroups_per_cu_without_scratch(isa):
-    source = open(SRC).read()
-    assert re.search(r"constexpr int kWorkgroupsPerCu = %d;" % WORKGROUPS_PER_CU, source)
-    total = 0
-    for n, text in isa.items():
-        kernels = _kernels(text)
-        descs = ac.descriptors(text)
-        assert len(kernels) == 2 and len(descs) == 2, (n, sorted(kernels), sorted(descs))          # complex and power, nothing else
-        total += len(kernels)
-        for name, body in kernels.items():
-            assert "pfb_real_kernelILi%dE" % n in name
-            assert not [line for line in body if line.startswith("scratch_")], name
-            assert not [line for line in body if re.match(r"v_(sin|cos)_", line)], name
-            assert not [line for line in body if re.match(r"v_pk_\w+_f32", line)], name
-            assert ac.descriptor_field(descs, name, "private_segment_fixed_size") == 0, name
-            vgprs, lds = ac.descriptor_field(descs, name, "next_free_vgpr"), ac.descriptor_field(descs, name, "group_segment_fixed_size")
-            print(f"N={n:5d} {'power  ' if 'ELi1EEE' in name else 'complex'}: {vgprs} VGPRs, {lds} B of LDS")
-            assert lds == 4096 // 16 * 17 * 8 and WORKGROUPS_PER_CU * lds <= LDS_PER_CU, name
-            assert vgprs <= VGPR_BUDGET, (name, vgprs)
-    assert total == 10
+    ac.check_pfb_kernel_rules(isa, "pfb_real_kernel")
 
 
 def test_signal_loads_of_a_tap_are_issued_together(isa):
-    """the sixteen signal loads of one tap (the kernel's only non-temporal loads) are contiguous in the instruction stream up to
-    address arithmetic, with no branch, barrier or vmcnt(0) between the first and the last, and sit in a loop (a backward branch
-    follows them); its sixteen coefficient pairs -- plain 8-byte loads -- follow them inside the loop"""
-    arithmetic = re.compile(r"(v_add|v_addc|v_lshl|v_lshlrev|v_mov|v_mad|v_ashr|v_and|v_or|s_add|s_addc|s_lshl|s_mov|s_nop|s_mul|s_waitcnt lgkmcnt|;)")
-    for n, text in isa.items():
-        for name, body in _kernels(text).items():
-            loads = [i for i, line in enumerate(body) if re.match(r"global_load_dwordx2 v\[\d+:\d+\], v\[\d+:\d+\], off( offset:-?\d+)? nt$", line)]
-            assert len(loads) == 16, (name, len(loads))
-            assert len([line for line in body if line.startswith("global_load") and line.endswith(" nt")]) == 16, name
-            between = body[loads[0]:loads[-1] + 1]
-            assert not [line for line in between if line.startswith(("s_cbranch", "s_branch", "s_setpc", "s_barrier"))], name
-            assert not [line for line in between if re.search(r"vmcnt\(0\)", line)], name
-            others = [line for line in between if line and not line.startswith("global_load_dwordx2")]
-            assert all(arithmetic.match(line) for line in others), (name, others)
-            # the loop: the first label before the loads is the target of the first branch after them
-            label = next(line for line in reversed(body[:loads[0]]) if re.match(r"\.LBB\d+_\d+:", line)).split(":")[0]
-            branch = next(line for line in body[loads[-1]:] if line.startswith("s_cbranch"))
-            assert branch.split()[-1] == label, (name, label, branch)
-            end = body.index(branch, loads[-1])
-            taps = [i for i in range(loads[-1] + 1, end) if re.match(r"global_load_dwordx2 v\[\d+:\d+\], v\[\d+:\d+\], off( offset:-?\d+)?$", body[i])]
-            assert len(taps) == 16, (name, len(taps))
+    """the signal loads are the kernel's only non-temporal loads; the coefficient pairs are plain 8-byte loads"""
+    ac.check_pfb_signal_loads(isa, "pfb_real_kernel", signal=r"global_load_dwordx2 v\[\d+:\d+\], v\[\d+:\d+\], off( offset:-?\d+)? nt$",
+                              tap=r"global_load_dwordx2 v\[\d+:\d+\], v\[\d+:\d+\], off( offset:-?\d+)?$",
+                              arithmetic=r"(v_add|v_addc|v_lshl|v_lshlrev|v_mov|v_mad|v_ashr|v_and|v_or|s_add|s_addc|s_lshl|s_mov|s_nop|s_mul|s_waitcnt lgkmcnt|;)")
 
 
 # ------------------------------------------------------------------------------------------------ C ABI
-NAMES = ("smfft_pfb_real_frames", "smfft_pfb_real_launch", "smfft_pfb_real_benchmark", "smfft_pfb_real_launch_tuned",
-         "smfft_pfb_real_default_tile_run")
-
-
 @pytest.fixture(scope="module")
 def pr():
     from smfft_amd import pfb_real
@@ -154,15 +93,10 @@ def pr():
 
 def test_header_declarations_equal_the_ctypes_signatures(pr):
     from smfft_amd import pfb
-    header = open(os.path.join(ROOT, "include", "smfft_pfb_real.h")).read()
-    for phrase in ("Out of scope", "oversampled", "complex prototypes", "synthesis", "Nyquist power", "NOT output", "N <= 128", "N >= 8192", "EVEN"):
-        assert phrase in header, phrase
-    decl = ac.declarations("smfft_pfb_real.h")
-    assert sorted(decl) == sorted(pr.SIGS) == sorted(NAMES)
-    for name, (res, args) in decl.items():
-        assert pr.SIGS[name] == ac.signature(res, args), name
+    ac.check_pfb_declarations(pr, "smfft_pfb_real", ("Out of scope", "oversampled", "complex prototypes", "synthesis", "Nyquist power", "NOT output", "N <= 128",
+                                                     "N >= 8192", "EVEN"))
     # one for one the complex bank's functions, in arguments and results
-    for name in NAMES:
+    for name in ac.pfb_names("smfft_pfb_real"):
         assert pr.SIGS[name] == pfb.SIGS[name.replace("pfb_real", "pfb")], name
     assert pr.SIZES == SIZES
     # the complex bank's header points real input here
@@ -170,35 +104,12 @@ def test_header_declarations_equal_the_ctypes_signatures(pr):
 
 
 def test_library_exports_exactly_the_five_symbols(pr):
-    nm = subprocess.run(["nm", "-D", "--defined-only", pr.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert sorted(re.findall(r" T (smfft_\w+)$", nm, re.M)) == sorted(NAMES)
+    ac.check_pfb_exports(pr, "smfft_pfb_real")
 
 
 def test_unsupported_combinations_return_minus_one_without_a_device(pr):
-    """all validation happens before any HIP call: these return -1 (or 0 when there is no whole frame) with no device and null pointers"""
-    lib = pr.lib()
-    t = ctypes.c_double(0.0)
-    bad = [(1 << 20, 1, n, 4) for n in (0, 128, 1000, 8192, -1024)] + [(1 << 20, 1, 1024, p) for p in (0, 33, -1)]
-    bad += [(1 << 20, c, 1024, 4) for c in (0, -1)] + [(-2, 1, 1024, 4), (-1, 1, 1024, 4)]
-    bad += [((1 << 20) + 1, 1, 1024, 4), (8 * 2048 + 1, 2, 1024, 4), (1, 1, 256, 1), (3, 1, 1024, 4)]      # odd lengths
-    for L, C, N, P in bad:
-        for power in (0, 1):
-            assert lib.smfft_pfb_real_launch(None, L, C, None, N, P, power, None, None) == -1, (L, C, N, P)
-            assert lib.smfft_pfb_real_launch_tuned(None, L, C, None, N, P, power, None, None, 3) == -1, (L, C, N, P)
-            assert lib.smfft_pfb_real_benchmark(None, L, C, None, N, P, power, None, ctypes.byref(t)) == -1, (L, C, N, P)
-    assert lib.smfft_pfb_real_launch_tuned(None, 1 << 20, 1, None, 1024, 4, 0, None, None, -1) == -1
-    # no whole frame is not an error: nothing is launched
-    for L in (0, 2046, 4 * 2048 - 2):
-        for power in (0, 1):
-            assert lib.smfft_pfb_real_launch(None, L, 2, None, 1024, 4, power, None, None) == 0
-            assert lib.smfft_pfb_real_launch_tuned(None, L, 2, None, 1024, 4, power, None, None, 7) == 0
-            assert lib.smfft_pfb_real_benchmark(None, L, 2, None, 1024, 4, power, None, ctypes.byref(t)) == 0
-    assert t.value == 0.0
-    for n in (0, 128, 1000, 8192):
-        assert lib.smfft_pfb_real_frames(1 << 20, n, 4) == -1 and lib.smfft_pfb_real_default_tile_run(n, 4) == -1
-    for p in (0, 33, -1):
-        assert lib.smfft_pfb_real_frames(1 << 20, 1024, p) == -1 and lib.smfft_pfb_real_default_tile_run(1024, p) == -1
-    assert lib.smfft_pfb_real_frames(-2, 1024, 4) == -1 and lib.smfft_pfb_real_frames((1 << 20) + 1, 1024, 4) == -1
+    ac.check_pfb_rejections(pr, "smfft_pfb_real", samples=2, bad_lengths=[(-2, 1, 1024, 4), (-1, 1, 1024, 4),
+                                                                          ((1 << 20) + 1, 1, 1024, 4), (8 * 2048 + 1, 2, 1024, 4), (1, 1, 256, 1), (3, 1, 1024, 4)])      # negative, odd
     with pytest.raises(ValueError):
         pr.frames(1000, 100, 4)
     with pytest.raises(ValueError):

@@ -2,8 +2,9 @@
 pieces, in one process, timed round robin so that drift of the box hits all alike (median of --reps event-timed launches each, every
 shape warmed up before its timed window):
   fused     smfft_pfb_launch_tuned for the run length R in {1, 4, 16, whole run = ceil(tiles / grid)} x signal loads {nt, plain}: the
-            second load policy is a second build of the library, given with --alt (the shipped one is smfft_amd/libsmfft_pfb.so or
-            SMFFT_PFB_LIB); the two builds' outputs are compared to the bit on the timed inputs
+            second load policy is a second build of the library, given with --alt PATH (the shipped one is smfft_amd/libsmfft_pfb.so
+            or SMFFT_PFB_LIB); further builds with --alt NAME=PATH (a parent commit's, say); all builds' outputs are compared to the bit
+            on the timed inputs, and every build's median is set against the shipped one's at the same R
                 make -C smfft_amd/csrc PFB_LIB=../../build_ab/libsmfft_pfb_plain.so PFB_OBJDIR=../../build_ab/pfb_plain PFB_NT_LOADS=0 \\
                      ../../build_ab/libsmfft_pfb_plain.so
   bare      smfft_launch (forward, external) of the same C F transforms on the same buffers: what the weighting costs on top (floor 1.0)
@@ -12,7 +13,7 @@ shape warmed up before its timed window):
   copy      a device copy that moves the same bytes, (C L + C F N) 8 (power mode: C L 8 + C F N 4): the same-run ceiling
 Main configuration: C = 1, N = 1024, P = 8, F = 524288 (4 GiB in, 4 GiB out, complex mode), the output from plain hipMalloc and from
 smfft_malloc_written_for; then N in {256, 4096} x P in {4, 8, 16} and power mode at the main shape.
-    python tools/ab_pfb.py [--reps 30] [--alt build_ab/libsmfft_pfb_plain.so]
+    python tools/ab_pfb.py [--reps 30] [--alt build_ab/libsmfft_pfb_plain.so] [--alt NAME=PATH ...] [--small]
     rocprofv3 --kernel-trace --stats -d DIR -- python tools/ab_pfb.py --trace        three launches of each kernel, nothing timed
     rocprofv3 --pmc FETCH_SIZE -d DIR -- python tools/ab_pfb.py --pmc                counters only (WRITE_SIZE: a run of its own)
     python tools/ab_pfb.py --pmc-report DIR [DIR ...]                                 fetched bytes / (C L 8) for R = 1 and the shipped R
@@ -24,18 +25,18 @@ import glob
 import os
 import re
 import sys
+import types
 
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
+import ab_pfb_common as ab  # noqa: E402
 
-WORKGROUPS_PER_CU = 3          # smfft_pfb.hip, kWorkgroupsPerCu
-MAIN = (1, 1024, 8, 1 << 19)   # C, N, P, F
 PMC_LAUNCHES = 3
 
 
 def pmc_report(dirs):
     """per counter: mean per dispatch of the bare transform, the R = 1 launches and the shipped-R launches (dispatch order of --pmc)"""
-    C, N, P, F = MAIN
+    C, N, P, F = ab.MAIN
     L = (F + P - 1) * N
     for d in dirs:
         files = sorted(glob.glob(d + "/**/*counter_collection.csv", recursive=True), key=os.path.getmtime)[-1:]
@@ -61,12 +62,10 @@ def pmc_report(dirs):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=30)
-    ap.add_argument("--alt", help="a second build of libsmfft_pfb.so (the other signal-load policy)")
     ap.add_argument("--trace", action="store_true")
     ap.add_argument("--pmc", action="store_true")
     ap.add_argument("--pmc-report", nargs="+")
-    ap.add_argument("--small", action="store_true", help="a sixteenth of every shape (a rehearsal, not a measurement)")
+    ab.add_arguments(ap, "libsmfft_pfb.so (a bare PATH: the other signal-load policy)")
     args = ap.parse_args()
     if args.pmc_report:
         return pmc_report(args.pmc_report)
@@ -78,38 +77,15 @@ def main():
     import smfft_amd as sm
     from smfft_amd import pfb
 
-    sm.FFT_init()
-    torch.cuda.init()
-    stream = torch.cuda.current_stream()
-    sp = stream.cuda_stream
-    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    ses = ab.Session(pfb, "smfft_pfb", args)
+    sp, gen = ses.sp, ses.gen
     # the shipped library's load policy is the default of its source
     src = open(os.path.join(ROOT, "smfft_amd", "csrc", "smfft_pfb.hip")).read()
-    libs = {"nt" if re.search(r"#define SMFFT_PFB_NT_LOADS (\d)", src).group(1) == "1" else "plain": pfb.lib()}
-    if args.alt:
-        libs["plain" if "nt" in libs else "nt"] = pfb.load(os.path.abspath(args.alt))
-    shipped = next(iter(libs))
-    gen = torch.Generator(device="cuda").manual_seed(0)
+    shipped = "nt" if re.search(r"#define SMFFT_PFB_NT_LOADS (\d)", src).group(1) == "1" else "plain"
+    libs = {shipped: pfb.lib()}
+    libs.update(ses.load(item, "plain" if shipped == "nt" else "nt") for item in args.alt)
 
-    def timed(fn):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(stream)
-        fn()
-        b.record(stream)
-        b.synchronize()
-        return a.elapsed_time(b)
-
-    def round_robin(fns, reps):
-        ts = {n: [] for n in fns}
-        for fn in fns.values():
-            fn(), fn()
-        torch.cuda.synchronize()
-        for _ in range(reps):
-            for name, fn in fns.items():
-                ts[name].append(timed(fn))
-        return {n: sorted(v) for n, v in ts.items()}
-
-    def shape(C, N, P, F, power, unfused=False, placed=False, only=None):
+    def shape(C, N, P, F, power, unfused=False, placed=False):
         """one shape: allocate, check, time, report; returns the medians"""
         if args.small:
             F //= 16
@@ -119,36 +95,22 @@ def main():
         x = torch.view_as_complex(torch.randn((C, L, 2), dtype=torch.float32, device="cuda", generator=gen))
         h = torch.from_numpy(pfb.prototype(N, P)).cuda()
         out = torch.empty((C, F, N), dtype=torch.float32 if power else torch.complex64, device="cuda")
-        tiles = -(-(C * F) // (4096 // N))
-        whole = -(-tiles // (cus * WORKGROUPS_PER_CU))
         default = pfb.default_tile_run(N, P)
-        what = f"C={C} N={N} P={P} F={F} {'power' if power else 'complex'}"
-        print(f"--- {what}: {C * L * 8 / 2**30:.2f} GiB in, {C * F * N * width / 2**30:.2f} GiB out, {tiles} tiles, whole run = {whole}, "
-              f"shipped R = {default}, shipped loads = {shipped}", flush=True)
+        what, runs = ses.start_shape(C, N, P, F, power, C * L * 8, default, f", shipped loads = {shipped}")
 
         def fused(lib, R, o):
-            def run():
-                rc = lib.smfft_pfb_launch_tuned(x.data_ptr(), L, C, h.data_ptr(), N, P, int(power), o.data_ptr(), sp, R)
-                assert rc == 0, rc
-            return run
+            return ses.fused(lib, x, L, C, h, N, P, power, o, R)
 
-        fns = {}
-        runs = (("R=1", 1), ("R=4", 4), ("R=16", 16), (f"R=whole({whole})", whole))
-        for policy, lib in libs.items():
-            for label, R in runs:
-                fns[f"fused {policy:5s} {label}"] = fused(lib, R, out)
-        if only:
-            fns = {k: v for k, v in fns.items() if only(k)}
+        fns = {f"fused {policy:5s} {label}": fused(lib, R, out) for policy, lib in libs.items() for label, R in runs}
         pw = ctypes.c_void_p()
         if placed:
             assert sm.lib.smfft_malloc_written_for(x.data_ptr(), out.numel() * width, ctypes.byref(pw)) == 0
-            fns[f"fused {shipped:5s} R=0 (shipped), output of smfft_malloc_written_for"] = fused(libs[shipped], 0, _Ptr(pw.value))
+            fns[f"fused {shipped:5s} R=0 (shipped), output of smfft_malloc_written_for"] = fused(libs[shipped], 0, types.SimpleNamespace(data_ptr=lambda: pw.value))
         fns[f"fused {shipped:5s} R=0 (shipped = {default})"] = fused(libs[shipped], 0, out)
+        bare = "bare smfft_launch, same C F transforms"
         if not power:
-            fns["bare smfft_launch, same C F transforms"] = lambda: sm.launch("ct", "external", x.data_ptr(), out.data_ptr(), N, C * F, False, True, stream=sp)
-        src = torch.empty(moved // 8, dtype=torch.float32, device="cuda").normal_(generator=gen)
-        dst = torch.empty_like(src)
-        fns["copy of the same bytes"] = lambda: dst.copy_(src)
+            fns[bare] = lambda: sm.launch("ct", "external", x.data_ptr(), out.data_ptr(), N, C * F, False, True, stream=sp)
+        fns[ab.COPY] = ses.copy_of(moved)
         if unfused:
             buf = torch.empty((C, F, N), dtype=torch.complex64, device="cuda")
             blocks = torch.view_as_real(x[:, :(F + P - 1) * N].view(C, F + P - 1, N))
@@ -168,47 +130,25 @@ def main():
             torch.cuda.synchronize()
             print(f"max |fused - unfused| / max |unfused| = {((out - ref).abs().max() / ref.abs().max()).item():.2e}", flush=True)
             del ref
-        # every schedule and both builds give the same bits on the timed inputs
-        base = None
-        for name, fn in fns.items():
-            if name.startswith("fused") and "malloc_written_for" not in name:
-                out.fill_(0)
-                fn()
-                torch.cuda.synchronize()
-                bits = out.view(torch.float32).view(torch.int32)
-                if base is None:
-                    base = bits.clone()
-                else:
-                    assert torch.equal(bits, base), f"{name}: bits differ"
+        # every schedule and every build give the same bits on the timed inputs
+        ab.compare_outputs({n: fn for n, fn in fns.items() if n.startswith("fused") and "malloc_written_for" not in n}, out, lambda name: True)
         print("all fused variants: identical bits", flush=True)
-        del base
         if args.trace or args.pmc:
             return None
-        ts = round_robin(fns, args.reps)
-        med = {n: v[len(v) // 2] for n, v in ts.items()}
-        copy = med["copy of the same bytes"]
-        for n, v in ts.items():
-            line = f"{n:66s} median {med[n]:8.3f} ms  min {v[0]:8.3f}  {moved / med[n] / 1e9:7.3f} TB/s  {copy / med[n]:.3f} of the copy"
-            if "bare smfft_launch, same C F transforms" in med and n.startswith("fused"):
-                line += f"  {med[n] / med['bare smfft_launch, same C F transforms']:.3f} x bare"
-            print(line, flush=True)
-        ship = med[f"fused {shipped:5s} R=0 (shipped = {default})"]
+        q = ab.report(ses.round_robin(fns), moved, 66, False,
+                      lambda n, q: f"  {q[n][1] / q[bare][1]:.3f} x bare" if bare in q and n.startswith("fused") else "")
+        ab.report_builds(q, [(f"{what} {label}", f"fused {shipped:5s} {label}", {b: f"fused {b:5s} {label}" for b in libs if b != shipped})
+                             for label, _ in runs])
+        ship = q[f"fused {shipped:5s} R=0 (shipped = {default})"][1]
         if unfused:
-            print(f"GATE  unfused / fused (shipped) = {med['unfused: torch weighting + smfft_launch'] / ship:.2f} x  (must be >= 2)", flush=True)
+            print(f"GATE  unfused / fused (shipped) = {q['unfused: torch weighting + smfft_launch'][1] / ship:.2f} x  (must be >= 2)", flush=True)
         if pw.value:
             sm.lib.smfft_free_written(pw.value)
-        return med
-
-    class _Ptr:
-        def __init__(self, p):
-            self.p = p
-
-        def data_ptr(self):
-            return self.p
+        return {n: v[1] for n, v in q.items()}
 
     if args.trace or args.pmc:
         # a few launches of each kernel, in a fixed order: bare, R = 1, shipped R (tools/ab_pfb.py --pmc-report relies on it)
-        C, N, P, F = MAIN
+        C, N, P, F = ab.MAIN
         if args.small:
             F //= 16
         L = (F + P - 1) * N
@@ -230,9 +170,8 @@ def main():
               f"({pfb.default_tile_run(N, P)}) at C={C} N={N} P={P} F={F}", flush=True)
         return
 
-    print(f"device: {torch.cuda.get_device_name(0)}, {cus} compute units, persistent grid {cus * WORKGROUPS_PER_CU} workgroups; {args.reps} reps round robin",
-          flush=True)
-    C, N, P, F = MAIN
+    ses.headline(libs)
+    C, N, P, F = ab.MAIN
     shape(C, N, P, F, False, unfused=True, placed=True)
     torch.cuda.empty_cache()
     shape(C, N, P, F, True)

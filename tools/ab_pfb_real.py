@@ -21,15 +21,12 @@ import sys
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
 
-WORKGROUPS_PER_CU = 3          # smfft_pfb_real.hip, kWorkgroupsPerCu
-MAIN = (1, 1024, 8, 1 << 19)   # C, N, P, F
+import ab_pfb_common as ab  # noqa: E402
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=30)
-    ap.add_argument("--alt", action="append", default=[], metavar="NAME=PATH", help="another build of libsmfft_pfb_real.so")
-    ap.add_argument("--small", action="store_true", help="a sixteenth of every shape (a rehearsal, not a measurement)")
+    ab.add_arguments(ap, "libsmfft_pfb_real.so")
     ap.add_argument("--main-only", action="store_true")
     args = ap.parse_args()
 
@@ -38,34 +35,10 @@ def main():
     import smfft_amd as sm
     from smfft_amd import pfb, pfb_real
 
-    sm.FFT_init()
-    torch.cuda.init()
-    stream = torch.cuda.current_stream()
-    sp = stream.cuda_stream
-    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    ses = ab.Session(pfb_real, "smfft_pfb_real", args)
+    sp, gen = ses.sp, ses.gen
     libs = {"shipped": pfb_real.lib()}
-    for item in args.alt:
-        name, path = item.split("=", 1)
-        libs[name] = pfb_real.load(os.path.abspath(path))
-    gen = torch.Generator(device="cuda").manual_seed(0)
-
-    def timed(fn):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(stream)
-        fn()
-        b.record(stream)
-        b.synchronize()
-        return a.elapsed_time(b)
-
-    def round_robin(fns, reps):
-        ts = {n: [] for n in fns}
-        for fn in fns.values():
-            fn(), fn()
-        torch.cuda.synchronize()
-        for _ in range(reps):
-            for name, fn in fns.items():
-                ts[name].append(timed(fn))
-        return {n: sorted(v) for n, v in ts.items()}
+    libs.update(ses.load(item) for item in args.alt)
 
     def shape(C, N, P, F, power, gate=False):
         if args.small:
@@ -76,38 +49,16 @@ def main():
         x = torch.randn((C, L), dtype=torch.float32, device="cuda", generator=gen)
         h = torch.from_numpy(pfb_real.prototype(N, P)).cuda()
         out = torch.empty((C, F, N), dtype=torch.float32 if power else torch.complex64, device="cuda")
-        tiles = -(-(C * F) // (4096 // N))
-        whole = -(-tiles // (cus * WORKGROUPS_PER_CU))
         default = pfb_real.default_tile_run(N, P)
-        what = f"C={C} N={N} P={P} F={F} {'power' if power else 'complex'}"
-        print(f"--- {what}: {C * L * 4 / 2**30:.2f} GiB in, {C * F * N * width / 2**30:.2f} GiB out, {tiles} tiles, whole run = {whole}, "
-              f"shipped R = {default}", flush=True)
+        what, runs = ses.start_shape(C, N, P, F, power, C * L * 4, default)
 
-        def fused(lib, R, o=out):
-            def run():
-                rc = lib.smfft_pfb_real_launch_tuned(x.data_ptr(), L, C, h.data_ptr(), N, P, int(power), o.data_ptr(), sp, R)
-                assert rc == 0, rc
-            return run
-
-        fns = {}
-        for label, R in (("R=1", 1), ("R=4", 4), ("R=16", 16), (f"R=whole({whole})", whole)):
-            fns[f"fused shipped {label}"] = fused(libs["shipped"], R)
+        fns = {f"fused shipped {label}": ses.fused(libs["shipped"], x, L, C, h, N, P, power, out, R) for label, R in runs}
         for name, lib in libs.items():
-            fns[f"fused {name} R=0 (default = {default})"] = fused(lib, 0)
+            fns[f"fused {name} R=0 (default = {default})"] = ses.fused(lib, x, L, C, h, N, P, power, out, 0)
         ship = f"fused shipped R=0 (default = {default})"
 
         # the schedules of the shipped build: the same bits; the other builds: their largest difference from it
-        base = None
-        for name, fn in fns.items():
-            out.fill_(0)
-            fn()
-            torch.cuda.synchronize()
-            if base is None:
-                base = out.clone()
-            elif name.startswith("fused shipped"):
-                assert torch.equal(out.view(torch.float32).view(torch.int32), base.view(torch.float32).view(torch.int32)), f"{name}: bits differ"
-            else:
-                print(f"max |{name} - shipped| / max |shipped| = {((out - base).abs().max() / base.abs().max()).item():.2e}", flush=True)
+        base = ab.compare_outputs(fns, out, lambda name: name.startswith("fused shipped"))
         print("all schedules of the shipped build: identical bits", flush=True)
 
         # the unfused pipeline from public pieces
@@ -141,16 +92,10 @@ def main():
         # the complex bank at the same N and F: the same bytes in and out
         # (the signal read as (F + P - 1) N float2 per stream, the first P N taps)
         fns["complex bank smfft_pfb_launch, same N and F (same bytes)"] = lambda: pfb.launch(x.data_ptr(), (F + P - 1) * N, C, h.data_ptr(), N, P, out.data_ptr(), power=power, stream=sp)
-        src = torch.empty(moved // 8, dtype=torch.float32, device="cuda").normal_(generator=gen)
-        dst = torch.empty_like(src)
-        fns["copy of the same bytes"] = lambda: dst.copy_(src)
+        fns[ab.COPY] = ses.copy_of(moved)
 
-        ts = round_robin(fns, args.reps)
-        q = {n: (v[len(v) // 4], v[len(v) // 2], v[(3 * len(v)) // 4]) for n, v in ts.items()}
-        copy = q["copy of the same bytes"][1]
-        for n, v in ts.items():
-            lo, med, hi = q[n]
-            print(f"{n:62s} median {med:8.3f} ms  quartiles {lo:8.3f} {hi:8.3f}  min {v[0]:8.3f}  {moved / med / 1e9:7.3f} TB/s  {copy / med:.3f} of the copy", flush=True)
+        q = ab.report(ses.round_robin(fns), moved, 62, True)
+        ab.report_builds(q, [(what + " R=0", ship, {b: f"fused {b} R=0 (default = {default})" for b in libs if b != "shipped"})])
         fm = q[ship][1]
         print(f"fused (shipped) / complex bank at the same bytes = {fm / q['complex bank smfft_pfb_launch, same N and F (same bytes)'][1]:.3f}", flush=True)
         if not power:
@@ -161,9 +106,8 @@ def main():
                 return ok
         return True
 
-    print(f"device: {torch.cuda.get_device_name(0)}, {cus} compute units, persistent grid {cus * WORKGROUPS_PER_CU} workgroups; {args.reps} reps round robin; "
-          f"builds: {', '.join(libs)}", flush=True)
-    C, N, P, F = MAIN
+    ses.headline(libs)
+    C, N, P, F = ab.MAIN
     ok = shape(C, N, P, F, False, gate=True)
     if not args.main_only:
         torch.cuda.empty_cache()

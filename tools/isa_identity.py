@@ -8,8 +8,12 @@ Compiles, on a checkout of BASE (git archive into a temporary directory) and on 
                                   (and the -I. of the three that include headers of that directory), where BASE has the file
   examples/*.hip                  the files BASE has
 to device assembly (hipcc -S --cuda-device-only) and compares every kernel BASE has, text of its body and its .amdhsa descriptor,
-with the basic-block labels (.LBB<f>_<n>) and the function-local symbols renumbered in order of appearance.
+with the basic-block labels (.LBB<f>_<n>) and the function-local symbols renumbered in order of appearance.  A kernel whose text differs
+gets a second verdict, "same up to scheduling": the same .amdhsa descriptor, instruction count and opcode histogram, and the same
+sequence of labels, memory instructions, barriers, waits and branches with register numbers blanked -- what is left to differ is the order
+of independent ALU and move instructions, register numbers and the operand order of commutative operations.  It still counts as differing.
     python tools/isa_identity.py [BASE=HEAD]        exit status 0: every kernel identical"""
+import collections
 import os
 import re
 import subprocess
@@ -84,6 +88,29 @@ def normalise(text):
     return "\n".join(l for l in lines if l.strip())
 
 
+ORDERED = re.compile(r"(global_|ds_|buffer_|flat_|scratch_|s_load|s_buffer_load|s_barrier|s_waitcnt|s_cbranch|s_branch|s_setpc|s_endpgm|\.L\d+:)")
+
+
+def same_up_to_scheduling(a, b):
+    """the relaxed verdict on two normalised kernel texts: (True, "") or (False, what differs first)"""
+    def parts(text):
+        lines = [l.strip() for l in text.split("\n")]
+        desc = [l for l in lines if l.startswith(".amdhsa_")]
+        code = [l for l in lines if not l.startswith(".") or re.match(r"\.L\d+:", l)]
+        insts = [l for l in code if not l.endswith(":")]
+        ordered = [re.sub(r"\b([vsa])(\d+|\[\d+:\d+\])", lambda m: m.group(1) + ("2+" if ":" in m.group(2) else ""), l) for l in code if ORDERED.match(l)]
+        return desc, insts, collections.Counter(l.split()[0] for l in insts), ordered
+    (da, ia, ha, oa), (db, ib, hb, ob) = parts(a), parts(b)
+    if da != db:
+        return False, "descriptor: " + "; ".join(f"{x} -> {y}" for x, y in zip(da, db) if x != y)
+    if len(ia) != len(ib) or ha != hb:
+        return False, f"{len(ia)} -> {len(ib)} instructions, opcodes " + ", ".join(f"{k} {ha[k]} -> {hb[k]}" for k in sorted(set(ha) | set(hb)) if ha[k] != hb[k])
+    if oa != ob:
+        i = next((i for i, (x, y) in enumerate(zip(oa, ob)) if x != y), min(len(oa), len(ob)))
+        return False, f"ordered instruction {i}: {oa[i:i + 1]} -> {ob[i:i + 1]}"
+    return True, ""
+
+
 def main():
     base = sys.argv[1] if len(sys.argv) > 1 else "HEAD"
     with tempfile.TemporaryDirectory() as tmp:
@@ -102,8 +129,11 @@ def main():
         a, b = kernels(asm[("base", name)]), kernels(asm[("tree", name)])
         for k, text in a.items():
             total += 1
-            if b.get(k) != text:
-                differ.append((name, k, "missing" if k not in b else "differs"))
+            if k not in b:
+                differ.append((name, k, "missing"))
+            elif b[k] != text:
+                same, what = same_up_to_scheduling(text, b[k])
+                differ.append((name, k, "differs, same up to scheduling" if same else "differs (" + what + ")"))
         added = sorted(set(b) - set(a))
         print(f"{name:32s} {len(a):4d} kernels of {base}: {len(a) - sum(1 for d in differ if d[0] == name):4d} identical"
               + (f"; {len(added)} new" if added else ""))
