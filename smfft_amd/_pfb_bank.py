@@ -1,4 +1,5 @@
-"""What the ctypes mirrors of the two polyphase filter banks share (smfft_amd.pfb: complex streams, smfft_amd.pfb_real: real streams):
+"""What the ctypes mirrors of the polyphase filter banks share (smfft_amd.pfb: complex streams, smfft_amd.pfb_real: real streams;
+smfft_amd.large_pfb, the complex bank at N = 8192 / 16384, takes the Bank below with its own lengths and its own tuned launch):
 the five entry points' signatures, the calls with their error messages, the prototype and the host-array round trip.  The libraries'
 C ABIs are one for one the same; a bank differs by its prefix, by the samples a frame takes per channel (1: N complex samples, 2: 2N
 real samples) and by the signal's dtype.  The public functions, with the documentation of what each bank computes, are the mirrors'."""
@@ -24,9 +25,10 @@ def sigs(prefix):
 
 
 class Bank:
-    def __init__(self, name, prefix, lib, real):
-        """name: the mirror's, for messages ("pfb"); prefix: of its C functions ("smfft_pfb"); lib: the mirror's lib(); real: real streams"""
-        self.name, self.prefix, self.lib, self.real = name, prefix, lib, real
+    def __init__(self, name, prefix, lib, real, sizes=SIZES):
+        """name: the mirror's, for messages ("pfb"); prefix: of its C functions ("smfft_pfb"); lib: the mirror's lib(); real: real streams;
+        sizes: the lengths the library serves"""
+        self.name, self.prefix, self.lib, self.real, self.sizes = name, prefix, lib, real, sizes
         self.per_channel = 2 if real else 1           # samples of a frame per channel: a frame is `per_channel * N` samples
         self.chunk = "2N" if real else "N"
 
@@ -36,7 +38,7 @@ class Bank:
     def frames(self, L, N, P):
         f = self.call("frames", L, N, P)
         if f < 0:
-            raise ValueError(f"{self.prefix}_frames(L={L}, N={N}, P={P}) -> {f}: N must be one of {SIZES}, "
+            raise ValueError(f"{self.prefix}_frames(L={L}, N={N}, P={P}) -> {f}: N must be one of {self.sizes}, "
                              f"1 <= P <= {MAX_TAPS_PER_CHANNEL}, L >= 0" + (" and even" if self.real else ""))
         return f
 
@@ -84,8 +86,8 @@ class Bank:
             raise ValueError("the signal and the prototype must be real (complex signals: smfft_amd.pfb)" if self.real else "the prototype must be real")
         N = int(n_channels)
         frame = self.per_channel * N
-        if N not in SIZES or taps.size % frame or not 1 <= taps.size // frame <= MAX_TAPS_PER_CHANNEL:
-            raise ValueError(f"smfft_amd.{self.name} serves N in {SIZES} with P {self.chunk} taps, 1 <= P <= {MAX_TAPS_PER_CHANNEL}, "
+        if N not in self.sizes or taps.size % frame or not 1 <= taps.size // frame <= MAX_TAPS_PER_CHANNEL:
+            raise ValueError(f"smfft_amd.{self.name} serves N in {self.sizes} with P {self.chunk} taps, 1 <= P <= {MAX_TAPS_PER_CHANNEL}, "
                              f"not N = {N} with {taps.size} taps")
         P = taps.size // frame
         x = np.ascontiguousarray(np.atleast_2d(x), dtype=np.float32 if self.real else np.complex64)
