@@ -13,7 +13,7 @@
 //     b*SA + a with SA = T + 2, so that pass 1's writes (lane u -> b*SA + u) are distinct mod 16 in every 16-lane group and pass
 //     2's reads (u -> (u mod 16)*SA + u/16 + const) distinct mod 32 in every 32-lane group.  Exchanges B and C are conflict free
 //     in natural order.  Image: 16 * SA float2 = N*8 + 256 B: 64.25 KiB (two workgroups per CU) / 128.25 KiB (one).
-//   * One region serves all three exchanges, so each is a write, a barrier, a read and a barrier: six barriers per FFT.
+//   * One region serves all three exchanges, so each is a write, a barrier, a read and a barrier: six barriers per FFT (large_transform).
 //   * Twiddles: per-N rows built at compile time from the fp64-rounded W_16384 octant (smfft_twiddles_16384.inc), so that the
 //     threads of a wave read consecutive (pass 4) or few (passes 2, 3) addresses; they are loaded per FFT from L2, not kept in
 //     VGPRs across the persistent loop, which keeps the kernel under 128 VGPRs (4 waves per SIMD) without scratch.
@@ -175,6 +175,53 @@ struct LargeEngine {
     }
 };
 
+// the six barriers and four passes between a thread's sixteen inputs r[c] = x[u + T*c] and its outputs y[q] = X[u + T*q]
+template <int N, int DIR>
+__device__ __forceinline__ void large_transform(const LargeEngine<N, DIR>& e, float2 (&r)[16], float2 (&y)[16], float2* lds) {
+    e.pass1_write(r, lds);
+    __syncthreads();
+    e.read_pass2(y, lds);
+    __syncthreads();
+    e.write_b(y, lds);
+    __syncthreads();
+    e.read_pass3(y, lds);
+    __syncthreads();
+    e.write_c(y, lds);
+    __syncthreads();
+    float2 v[16];
+    e.read_c(v, lds);
+    __syncthreads();      // the image is free for the caller's next exchange
+    e.pass4(v, y);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Uniform values in scalar registers, for the kernels whose addresses are a per-workgroup base and a 32-bit lane offset
+// ------------------------------------------------------------------------------------------------
+typedef __attribute__((address_space(1))) const float2 GlobalFloat2;
+
+// a value that is the same in every lane, moved to a scalar register (a 32-bit division leaves its uniform quotient in a vector one,
+// and everything derived from it -- base pointers, bounds -- would follow it there)
+__device__ __forceinline__ unsigned uniform(unsigned v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (unsigned)__builtin_amdgcn_readfirstlane((int)v);
+#else
+    return v;
+#endif
+}
+__device__ __forceinline__ long long uniform(long long v) {
+    return (long long)(((unsigned long long)uniform((unsigned)((unsigned long long)v >> 32)) << 32) | uniform((unsigned)v));
+}
+
+// A uniform pointer, pinned to a scalar register pair (and hidden from the optimiser): a load through it takes the scalar base and one
+// 32-bit lane offset.  Left alone, the sixteen row addresses of a tap -- too far apart for the instruction's immediate offset -- become
+// sixteen 64-bit vector additions per row, or vector pointers carried round the tap loop.  The pointer must be the same in every lane:
+// for one that is not, the compiler silently takes the first active lane's (a readfirstlane).  On the host the statement is inert.
+template <class Ptr>
+__device__ __forceinline__ Ptr scalar_base(Ptr p) {
+    asm volatile("" : "+s"(p));
+    return p;
+}
+
 // ------------------------------------------------------------------------------------------------
 // The kernel: a persistent grid, FFT f = blockIdx.x, blockIdx.x + gridDim.x, ... < nFFTs.
 // amdgpu_waves_per_eu(4): at most 128 VGPRs, so that 16 waves (one 16384 or two 8192 workgroups) fit a CU.
@@ -191,20 +238,7 @@ __global__ __launch_bounds__(N / 16) __attribute__((amdgpu_waves_per_eu(4))) voi
         const long next = f + gridDim.x;
         e.reload_twiddles();
         e.load(r, d_input + f * N);
-        e.pass1_write(r, lds);
-        __syncthreads();
-        e.read_pass2(y, lds);
-        __syncthreads();
-        e.write_b(y, lds);
-        __syncthreads();
-        e.read_pass3(y, lds);
-        __syncthreads();
-        e.write_c(y, lds);
-        __syncthreads();
-        float2 v[16];
-        e.read_c(v, lds);
-        __syncthreads();      // the image is free for the next FFT's exchange A
-        e.pass4(v, y);
+        large_transform<N, DIR>(e, r, y, lds);      // its last barrier frees the image for the next FFT's exchange A
         e.store(y, d_output + f * N);
         if (next >= nFFTs) break;
         f = next;

@@ -40,40 +40,6 @@
 namespace smfft {
 namespace large {
 
-// the six barriers and four passes between a thread's sixteen inputs r[c] = x[u + T*c] and its outputs y[q] = X[u + T*q]
-template <int N, int DIR>
-__device__ __forceinline__ void large_transform(const LargeEngine<N, DIR>& e, float2 (&r)[16], float2 (&y)[16], float2* lds) {
-    e.pass1_write(r, lds);
-    __syncthreads();
-    e.read_pass2(y, lds);
-    __syncthreads();
-    e.write_b(y, lds);
-    __syncthreads();
-    e.read_pass3(y, lds);
-    __syncthreads();
-    e.write_c(y, lds);
-    __syncthreads();
-    float2 v[16];
-    e.read_c(v, lds);
-    __syncthreads();      // the image is free for the next transform's exchange A
-    e.pass4(v, y);
-}
-
-typedef __attribute__((address_space(1))) const float2 GlobalFloat2;
-
-// a value that is the same in every lane, moved to a scalar register (a 32-bit division leaves its uniform quotient in a vector one,
-// and everything derived from it -- base pointers, bounds -- would follow it there)
-__device__ __forceinline__ unsigned uniform(unsigned v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return (unsigned)__builtin_amdgcn_readfirstlane((int)v);
-#else
-    return v;
-#endif
-}
-__device__ __forceinline__ long long uniform(long long v) {
-    return (long long)(((unsigned long long)uniform((unsigned)((unsigned long long)v >> 32)) << 32) | uniform((unsigned)v));
-}
-
 // The stride of a persistent grid of `grid` workgroups over the units (c S + s) groups + g, in the units' own digits:
 // grid = (dc S + ds) groups + dg.  Computed by the host for the launch it makes; the kernel advances (c, s, g) by it.
 struct LargeFirStride {

@@ -25,8 +25,8 @@
 // only signal[c L, c L + (F + P - 1) N), taps[0, P N) and out[0, C F N) touched; the three must not overlap.
 #pragma once
 #include <hip/hip_runtime.h>
-#include "smfft_large_fir.hpp"      // large_transform, uniform, GlobalFloat2
-#include "smfft_pfb.hpp"            // smfft::PfbPlan (smfft_amd/csrc)
+#include "smfft_large.hpp"      // LargeEngine, large_transform, uniform, scalar_base, GlobalFloat2
+#include "smfft_pfb.hpp"        // smfft::PfbPlan (smfft_amd/csrc)
 
 namespace smfft {
 namespace large {
@@ -73,16 +73,6 @@ __device__ __forceinline__ float2 large_pfb_signal_load(GlobalFloat2* p, unsigne
     } else {
         return make_float2(p[u].x, p[u].y);
     }
-}
-
-// A uniform pointer, pinned to a scalar register pair (and hidden from the optimiser): a load through it takes the scalar base and one
-// 32-bit lane offset.  Left alone, the sixteen row addresses of a tap -- too far apart for the instruction's immediate offset -- become
-// sixteen 64-bit vector additions per row, or vector pointers carried round the tap loop.  The pointer must be the same in every lane:
-// for one that is not, the compiler silently takes the first active lane's (a readfirstlane).  On the host the statement is inert.
-template <class Ptr>
-__device__ __forceinline__ Ptr scalar_base(Ptr p) {
-    asm volatile("" : "+s"(p));
-    return p;
 }
 
 // nothing is scheduled across this point: the sixteen signal loads of a tap stay together and the coefficient loads go out after them

@@ -136,20 +136,8 @@ __global__ __launch_bounds__(N / 32) __attribute__((amdgpu_waves_per_eu(4))) voi
         const long next = f + gridDim.x;
         e.reload_twiddles();
         e.load(r, in + f * L);
-        e.pass1_write(r, lds);
-        __syncthreads();
-        e.read_pass2(y, lds);
-        __syncthreads();
-        e.write_b(y, lds);
-        __syncthreads();
-        e.read_pass3(y, lds);
-        __syncthreads();
-        e.write_c(y, lds);
-        __syncthreads();
+        large_transform<L, 0>(e, r, y, lds);      // its last barrier frees the image for exchange S
         float2 v[16];
-        e.read_c(v, lds);
-        __syncthreads();      // the image is free for exchange S
-        e.pass4(v, y);
         s.write(y, lds);
         __syncthreads();
         s.read_partner(v, lds);
@@ -182,20 +170,7 @@ __global__ __launch_bounds__(N / 32) __attribute__((amdgpu_waves_per_eu(4))) voi
         s.read_partner(y, lds);
         __syncthreads();      // the image is free for exchange A
         s.apply(r, y, vu);
-        e.pass1_write(r, lds);
-        __syncthreads();
-        e.read_pass2(y, lds);
-        __syncthreads();
-        e.write_b(y, lds);
-        __syncthreads();
-        e.read_pass3(y, lds);
-        __syncthreads();
-        e.write_c(y, lds);
-        __syncthreads();
-        float2 v[16];
-        e.read_c(v, lds);
-        __syncthreads();      // the image is free for the next FFT's exchange S
-        e.pass4(v, y);
+        large_transform<L, 1>(e, r, y, lds);      // its last barrier frees the image for the next FFT's exchange S
         e.store(y, out + f * L);
         if (next >= nFFTs) break;
         f = next;

@@ -4,7 +4,7 @@
 #include <cstring>
 #include <string>
 
-#include "hostsim.hpp"
+#include "host_entry.hpp"
 #include "smfft/smfft_large_fir.hpp"
 
 namespace {
@@ -49,23 +49,8 @@ const Kernel* find(const char* name) {
 }
 
 hostsim::Config config(int N, int grid, int schedule, unsigned long long seed, int blocks_descending, int knock_out, int period) {
-    hostsim::Config cfg;
-    cfg.grid = grid;
-    cfg.threads = N / 16;
-    cfg.schedule = schedule;
-    cfg.seed = seed;
-    cfg.blocks_descending = blocks_descending != 0;
-    cfg.knock_out = knock_out;
-    cfg.period = period;
-    cfg.lds_bytes = N == 8192 ? (size_t)smfft::large::LargeGeometry<8192>::kLdsBytes : (size_t)smfft::large::LargeGeometry<16384>::kLdsBytes;
-    return cfg;
-}
-
-int finish(const hostsim::Result& r, long* barriers) {
-    last_error = r.message;
-    if (barriers)
-        for (size_t i = 0; i < r.barriers.size(); ++i) barriers[i] = r.barriers[i];
-    return r.error;
+    const size_t lds = N == 8192 ? smfft::large::LargeGeometry<8192>::kLdsBytes : smfft::large::LargeGeometry<16384>::kLdsBytes;
+    return hostsim::config(N / 16, lds, grid, schedule, seed, blocks_descending, knock_out, period);
 }
 
 }  // namespace
@@ -93,13 +78,11 @@ int hostsim_large_fir_run(const char* name, const void* x, const void* H, void* 
     const long long units = w.segments() * C * ((K + group_size - 1) / group_size);
     if (units_out) *units_out = units;
     std::vector<hostsim::Watch> watched;
-    if (guard_bytes > 0) {
-        watched.push_back({x, (size_t)C * L * 8, (size_t)guard_bytes});
-        watched.push_back({H, (size_t)K * k->N * 8, (size_t)guard_bytes});
-        watched.push_back({y, (size_t)C * K * L * 8, (size_t)guard_bytes});
-    }
+    hostsim::watch(watched, guard_bytes, x, (size_t)C * L * 8);
+    hostsim::watch(watched, guard_bytes, H, (size_t)K * k->N * 8);
+    hostsim::watch(watched, guard_bytes, y, (size_t)C * K * L * 8);
     const hostsim::Config cfg = config(k->N, grid, schedule, seed, blocks_descending, knock_out, period);
-    return finish(k->fir(cfg, watched, (const float2*)x, (const float2*)H, (float2*)y, w, K, group_size, units), barriers);
+    return hostsim::finish(k->fir(cfg, watched, (const float2*)x, (const float2*)H, (float2*)y, w, K, group_size, units), barriers, last_error);
 }
 
 // Runs the prepare kernel `name` on K filters of M taps.
@@ -112,12 +95,10 @@ int hostsim_large_fir_prepare(const char* name, const void* taps, int M, int K, 
         return -1;
     }
     std::vector<hostsim::Watch> watched;
-    if (guard_bytes > 0) {
-        watched.push_back({taps, (size_t)K * M * 8, (size_t)guard_bytes});
-        watched.push_back({spectra, (size_t)K * k->N * 8, (size_t)guard_bytes});
-    }
+    hostsim::watch(watched, guard_bytes, taps, (size_t)K * M * 8);
+    hostsim::watch(watched, guard_bytes, spectra, (size_t)K * k->N * 8);
     const hostsim::Config cfg = config(k->N, grid, schedule, seed, 0, -1, 0);
-    return finish(k->prepare(cfg, watched, (const float2*)taps, M, K, correlate, (float2*)spectra), barriers);
+    return hostsim::finish(k->prepare(cfg, watched, (const float2*)taps, M, K, correlate, (float2*)spectra), barriers, last_error);
 }
 
 }  // extern "C"

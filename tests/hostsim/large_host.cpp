@@ -3,7 +3,7 @@
 #include <cstring>
 #include <string>
 
-#include "hostsim.hpp"
+#include "host_entry.hpp"
 #include "smfft/smfft_large_real.hpp"
 
 namespace {
@@ -59,26 +59,12 @@ int hostsim_large_run(const char* name, const void* d_input, void* d_output, int
                       int blocks_descending, int knock_out, int period, long guard_bytes, long* barriers) {
     for (const Kernel& k : kKernels) {
         if (std::strcmp(k.name, name) != 0) continue;
-        hostsim::Config cfg;
-        cfg.grid = grid;
-        cfg.threads = k.threads;
-        cfg.schedule = schedule;
-        cfg.seed = seed;
-        cfg.blocks_descending = blocks_descending != 0;
-        cfg.knock_out = knock_out;
-        cfg.period = period;
-        cfg.lds_bytes = (size_t)k.lds_bytes;
+        const hostsim::Config cfg = hostsim::config(k.threads, (size_t)k.lds_bytes, grid, schedule, seed, blocks_descending, knock_out, period);
         std::vector<hostsim::Watch> watched;
-        if (guard_bytes > 0) {
-            const size_t bytes = (size_t)k.fft_bytes * (size_t)(nFFTs > 0 ? nFFTs : 0);
-            watched.push_back({d_input, bytes, (size_t)guard_bytes});
-            if (d_output != d_input) watched.push_back({d_output, bytes, (size_t)guard_bytes});
-        }
-        const hostsim::Result r = k.run(cfg, watched, d_input, d_output, nFFTs);
-        last_error = r.message;
-        if (barriers)
-            for (size_t i = 0; i < r.barriers.size(); ++i) barriers[i] = r.barriers[i];
-        return r.error;
+        const size_t bytes = (size_t)k.fft_bytes * (size_t)(nFFTs > 0 ? nFFTs : 0);
+        hostsim::watch(watched, guard_bytes, d_input, bytes);
+        if (d_output != d_input) hostsim::watch(watched, guard_bytes, d_output, bytes);
+        return hostsim::finish(k.run(cfg, watched, d_input, d_output, nFFTs), barriers, last_error);
     }
     last_error = std::string("unknown kernel ") + name;
     return -1;

@@ -2,7 +2,7 @@
 // host against tests/hostsim/hip/hip_runtime.h) behind a C entry point that runs them through the executor.
 #include <string>
 
-#include "hostsim.hpp"
+#include "host_entry.hpp"
 #include "smfft/smfft_large_pfb.hpp"
 
 namespace {
@@ -48,26 +48,13 @@ int hostsim_large_pfb_run(int N, int power, const void* x, const void* h, void* 
         grid_out[1] = sched.form;
     }
     std::vector<hostsim::Watch> watched;
-    if (guard_bytes > 0) {
-        watched.push_back({x, (size_t)C * L * 8, (size_t)guard_bytes});
-        watched.push_back({h, (size_t)P * N * 4, (size_t)guard_bytes});
-        watched.push_back({y, (size_t)plan.pairs() * N * (power ? 4 : 8), (size_t)guard_bytes});
-    }
-    hostsim::Config cfg;
-    cfg.grid = sched.grid;
-    cfg.threads = N / 16;
-    cfg.schedule = schedule;
-    cfg.seed = seed;
-    cfg.blocks_descending = blocks_descending != 0;
-    cfg.knock_out = knock_out;
-    cfg.period = period;
-    cfg.lds_bytes = N == 8192 ? (size_t)smfft::large::LargeGeometry<8192>::kLdsBytes : (size_t)smfft::large::LargeGeometry<16384>::kLdsBytes;
+    hostsim::watch(watched, guard_bytes, x, (size_t)C * L * 8);
+    hostsim::watch(watched, guard_bytes, h, (size_t)P * N * 4);
+    hostsim::watch(watched, guard_bytes, y, (size_t)plan.pairs() * N * (power ? 4 : 8));
+    const size_t lds = N == 8192 ? smfft::large::LargeGeometry<8192>::kLdsBytes : smfft::large::LargeGeometry<16384>::kLdsBytes;
+    const hostsim::Config cfg = hostsim::config(N / 16, lds, sched.grid, schedule, seed, blocks_descending, knock_out, period);
     const Launcher launcher = N == 8192 ? (power ? run_pfb<8192, 1> : run_pfb<8192, 0>) : (power ? run_pfb<16384, 1> : run_pfb<16384, 0>);
-    const hostsim::Result r = launcher(cfg, watched, (const float2*)x, (const float*)h, y, plan, sched);
-    last_error = r.message;
-    if (barriers)
-        for (size_t i = 0; i < r.barriers.size(); ++i) barriers[i] = r.barriers[i];
-    return r.error;
+    return hostsim::finish(launcher(cfg, watched, (const float2*)x, (const float*)h, y, plan, sched), barriers, last_error);
 }
 
 }  // extern "C"

@@ -3,7 +3,7 @@
 #include <cstring>
 #include <string>
 
-#include "hostsim.hpp"
+#include "host_entry.hpp"
 #include <hip/hip_runtime.h>
 
 namespace {
@@ -46,23 +46,12 @@ const char* hostsim_toy_last_error() { return toy_error.c_str(); }
 int hostsim_toy_run(int fault, const float* in, float* out, int rounds, int grid, int schedule, unsigned long long seed, int blocks_descending,
                     int knock_out, int period, long guard_bytes, long* barriers) {
     if (fault < 0 || fault > 6) return -1;
-    hostsim::Config cfg;
-    cfg.grid = grid;
-    cfg.threads = kToyThreads;
-    cfg.schedule = schedule;
-    cfg.seed = seed;
-    cfg.blocks_descending = blocks_descending != 0;
-    cfg.knock_out = knock_out;
-    cfg.period = period;
-    cfg.lds_bytes = sizeof(float) * kToyLds;
+    const hostsim::Config cfg = hostsim::config(kToyThreads, sizeof(float) * kToyLds, grid, schedule, seed, blocks_descending, knock_out, period);
     std::vector<hostsim::Watch> watched;
     const size_t bytes = sizeof(float) * kToyThreads * (size_t)rounds * (size_t)grid;
-    if (guard_bytes > 0) watched = {{in, bytes, (size_t)guard_bytes}, {out, bytes, (size_t)guard_bytes}};
-    const hostsim::Result r = hostsim::launch(cfg, watched, kToys[fault], in, out, rounds);
-    toy_error = r.message;
-    if (barriers)
-        for (size_t i = 0; i < r.barriers.size(); ++i) barriers[i] = r.barriers[i];
-    return r.error;
+    hostsim::watch(watched, guard_bytes, in, bytes);
+    hostsim::watch(watched, guard_bytes, out, bytes);
+    return hostsim::finish(hostsim::launch(cfg, watched, kToys[fault], in, out, rounds), barriers, toy_error);
 }
 
 }  // extern "C"

@@ -13,7 +13,6 @@ barriers are sufficient.
 The host library is built on demand into pytest's temporary directory."""
 import ctypes
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -21,16 +20,13 @@ import pytest
 
 from oracle.np_reference import MAX_ABS_TOL, REL_L2_TOL
 from tests import test_fir_gpu as fg
-from tests import test_large_hostsim as lh
+from tests import hostsim_harness as hh
+from tests.hostsim_harness import GUARD, OUT_WORD, guarded as _guarded, payload as _payload, rand_complex as _rand
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import large_fir_model as lfm  # noqa: E402
 
-HOSTSIM = os.path.join(ROOT, "tests", "hostsim")
-GUARD = 4096
-GUARD_WORD = 0x7FC5A5A5    # a NaN of the guards' own
-OUT_WORD = 0xFFFFFFFF      # the NaN the output is prefilled with
 RECOMPUTE_8192, HELD_8192, RECOMPUTE_16384 = "large_fir<8192, 0>", "large_fir<8192, 1>", "large_fir<16384, 0>"
 FORMS = (RECOMPUTE_8192, HELD_8192, RECOMPUTE_16384)
 MODES = ("convolve", "correlate")
@@ -69,12 +65,12 @@ class FirHost:
         spec, s0 = _guarded(np.zeros((K, n), np.complex64), OUT_WORD)
         before = taps.copy()
         rc = self.lib.hostsim_large_fir_prepare(f"large_fir_prepare<{n}>".encode(), taps.ctypes.data + t0, M, K, int(mode == "correlate"),
-                                                spec.ctypes.data + s0, grid, lh.ASC, 0, GUARD, None)
+                                                spec.ctypes.data + s0, grid, hh.ASC, 0, GUARD, None)
         assert rc == 0, self.lib.hostsim_large_fir_last_error().decode()
         assert np.array_equal(taps, before)
         return _payload(spec, s0, (K, n))
 
-    def run(self, name, x, H, M, mode, group=1, grid=2, sched=lh.ASC, seed=0, desc=0, knock_out=-1, period=0):
+    def run(self, name, x, H, M, mode, group=1, grid=2, sched=hh.ASC, seed=0, desc=0, knock_out=-1, period=0):
         """-> ((C, K, L) output, barriers per workgroup, units); the three buffers sit between guard bands, the output NaN-prefilled"""
         C, L = x.shape
         K = H.shape[0]
@@ -94,42 +90,11 @@ class FirHost:
         return _payload(ys, y0, (C, K, L)), list(bars), units.value
 
 
-def _guarded(a, fill=None):
-    """GUARD bytes, 8 more, the data, GUARD bytes -> (words, byte offset of the data)"""
-    words = np.full((2 * GUARD + 8 + a.nbytes) // 4, GUARD_WORD, dtype=np.uint32)
-    lo = (GUARD + 8) // 4
-    words[lo:lo + a.nbytes // 4] = lh._bits(a) if fill is None else fill
-    return words, GUARD + 8
-
-
-def _payload(words, off, shape):
-    n = int(np.prod(shape)) * 2
-    return words[off // 4:off // 4 + n].view(np.complex64).reshape(shape).copy()
-
-
 @pytest.fixture(scope="module")
 def host(tmp_path_factory):
     """the build that contracts, as the device does"""
-    cxx = lh._compiler()
-    if cxx is None:
-        pytest.skip("no clang++ that can build the host stub (address_space / ext_vector_type need clang)")
     out = str(tmp_path_factory.mktemp("hostsim_fir"))
-    flags = ["-ffp-contract=fast"] + (["-mfma"] if lh._cpu_has_fma() else [])
-    common = [cxx, "-std=c++17", "-O2", "-fPIC", "-I" + HOSTSIM, "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "smfft_amd", "csrc")] + flags
-    objs, procs = [], []
-    for src in ("large_fir_host.cpp", "hostsim.cpp"):      # hostsim.cpp last: its guard closes the LDS section
-        objs.append(os.path.join(out, src.replace(".cpp", ".o")))
-        procs.append(subprocess.Popen(common + ["-c", os.path.join(HOSTSIM, src), "-o", objs[-1]], stderr=subprocess.PIPE, text=True))
-    for p in procs:
-        err = p.communicate()[1]
-        assert p.returncode == 0, err[-3000:]
-    lib = os.path.join(out, "libsmfft_large_fir_hostsim.so")
-    subprocess.check_call([cxx, "-shared", "-o", lib] + objs)
-    return FirHost(lib)
-
-
-def _rand(rng, shape):
-    return (rng.standard_normal(shape) + 1j * rng.standard_normal(shape)).astype(np.complex64)
+    return FirHost(hh.build(["large_fir_host.cpp"], "libsmfft_large_fir_hostsim.so", out, hh.fma_flags(), csrc_includes=True))
 
 
 def _group(name, K):
@@ -217,9 +182,9 @@ def test_host_schedule_invariance(host, name):
     group = _group(name, 2)
     base, bars, units = host.run(name, x, H, M, "convolve", group=group, grid=1)
     assert bars == _expected_barriers(name, units, 1, 2, group)
-    for sched, seed, desc in lh.SCHEDULES:
+    for sched, seed, desc in hh.SCHEDULES:
         got, b, _ = host.run(name, x, H, M, "convolve", group=group, grid=2 if not _held(name) else 1, sched=sched, seed=seed, desc=desc)
-        assert lh._same(got, base), f"{name}: schedule {sched} seed {seed} workgroups descending={desc} changes the bits"
+        assert hh.same(got, base), f"{name}: schedule {sched} seed {seed} workgroups descending={desc} changes the bits"
         assert sum(b) == sum(bars)
 
 
@@ -232,7 +197,7 @@ def test_host_k_filters_equal_k_single_launches(host, name, mode):
     got, _, _ = host.run(name, x, H, M, mode, group=_group(name, 3), grid=2)
     for k in range(3):
         one, _, _ = host.run(name, x, H[k:k + 1], M, mode, grid=1)
-        assert lh._same(one[0, 0], got[0, k]), (name, mode, k)
+        assert hh.same(one[0, 0], got[0, k]), (name, mode, k)
 
 
 @pytest.mark.parametrize("mode", MODES)
@@ -243,7 +208,7 @@ def test_host_held_equals_recompute(host, mode):
     want, _, _ = host.run(RECOMPUTE_8192, x, H, M, mode, grid=2)
     for group in (1, 2, 3):
         got, _, _ = host.run(HELD_8192, x, H, M, mode, group=group, grid=2)
-        assert lh._same(got, want), (mode, group)
+        assert hh.same(got, want), (mode, group)
 
 
 # ---- 5. barrier knock-out ------------------------------------------------------------------------------------------------------------------------
@@ -264,19 +229,10 @@ def test_host_barrier_knock_out(host, name):
     n, M, x, h = _small_case(name)
     H = host.prepare(n, h, "convolve")
     group = _group(name, 2)
-    base, bars, units = host.run(name, x, H, M, "convolve", group=group, grid=1)
-    assert bars == [period * units]
-    order = sorted(lh.SCHEDULES, key=lambda s: s[0] != lh.DESC)
-    for k, entry in enumerate(table):
-        differs = None
-        for sched, seed, desc in order:
-            got, b, _ = host.run(name, x, H, M, "convolve", group=group, grid=1, sched=sched, seed=seed, desc=desc, knock_out=k, period=period)
-            assert b == bars
-            if not lh._same(got, base):
-                differs = (sched, seed, desc)
-                break
-        print(f"{name} barrier {k}: {'differs under ' + str(differs) if differs else 'bit-identical under all schedules'}")
-        if entry == "needed":
-            assert differs, f"{name}: barrier {k} is entered as needed, but no schedule shows a difference without it"
-        else:
-            assert not differs, f"{name}: barrier {k} is entered as redundant, but schedule {differs} differs without it"
+
+    def run_base():
+        base, bars, units = host.run(name, x, H, M, "convolve", group=group, grid=1)
+        assert bars == [period * units]
+        return base, bars
+    hh.knock_out(table, run_base, lambda k, sched, seed, desc: host.run(name, x, H, M, "convolve", group=group, grid=1, sched=sched, seed=seed, desc=desc,
+                                                                        knock_out=k, period=period)[:2], name)

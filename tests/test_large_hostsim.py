@@ -15,26 +15,17 @@ give different bits under the schedules `ascending` and `descending`, which orde
 The host library is built on demand into pytest's temporary directory."""
 import ctypes
 import math
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from oracle import np_reference as ref
+from tests import hostsim_harness as hh
+from tests.hostsim_harness import ASC, DESC, GUARD, GUARD_WORD, RANDOM, SCHEDULES
+from tests.hostsim_harness import bits as _bits, same as _same
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOSTSIM = os.path.join(ROOT, "tests", "hostsim")
 G = 3                      # host grid
 NFFTS = 3 * G + 1          # three full rounds and a ragged one: workgroup 0 carries its image three times
-GUARD = 4096
-GUARD_WORD = 0x7FC5A5A5    # a NaN of the guards' own, not the LDS prefill
-
-ASC, DESC, WAVES, RANDOM = 0, 1, 2, 3
-SEEDS = (1, 2, 3, 4)
-# (schedule, seed, workgroups in descending order)
-SCHEDULES = [(s, seed, d) for d in (0, 1) for s, seeds in ((ASC, (0,)), (DESC, (0,)), (WAVES, SEEDS), (RANDOM, SEEDS)) for seed in seeds]
 
 # ---- item 5: every barrier of every kernel's loop, in program order ------------------------------------------------------------------
 # `needed`: the run without it differs from the shipped run under some schedule.  `redundant: reason`: bit-identical under all
@@ -69,20 +60,6 @@ def _kind(name):
 
 
 # ---- the host library ---------------------------------------------------------------------------------------------------------------
-def _compiler():
-    for c in ("/opt/rocm/llvm/bin/clang++", "/opt/rocm/lib/llvm/bin/clang++", shutil.which("clang++")):
-        if c and os.path.exists(c):
-            return c
-    return None
-
-
-def _cpu_has_fma():
-    try:
-        return any(" fma " in line + " " for line in open("/proc/cpuinfo") if line.startswith("flags"))
-    except OSError:
-        return False
-
-
 class HostLib:
     def __init__(self, path):
         self.lib = lib = ctypes.CDLL(path)
@@ -118,30 +95,11 @@ class HostLib:
         return rc, self.lib.hostsim_toy_last_error().decode(), list(bars)[:grid]
 
 
-def _build(cxx, outdir, fp_flags):
-    os.makedirs(outdir, exist_ok=True)
-    common = [cxx, "-std=c++17", "-O2", "-fPIC", "-I" + HOSTSIM, "-I" + os.path.join(ROOT, "include")] + fp_flags
-    objs, procs = [], []
-    for src in ("large_host.cpp", "toy_kernels.cpp", "hostsim.cpp"):      # hostsim.cpp last: its guard closes the LDS section
-        obj = os.path.join(outdir, src.replace(".cpp", ".o"))
-        objs.append(obj)
-        procs.append(subprocess.Popen(common + ["-c", os.path.join(HOSTSIM, src), "-o", obj], stderr=subprocess.PIPE, text=True))
-    for p in procs:
-        err = p.communicate()[1]
-        assert p.returncode == 0, err[-3000:]
-    lib = os.path.join(outdir, "libsmfft_large_hostsim.so")
-    subprocess.check_call([cxx, "-shared", "-o", lib] + objs)
-    return HostLib(lib)
-
-
 @pytest.fixture(scope="module")
 def builds(tmp_path_factory):
-    cxx = _compiler()
-    if cxx is None:
-        pytest.skip("no clang++ that can build the host stub (address_space / ext_vector_type need clang)")
     base = tmp_path_factory.mktemp("hostsim")
-    fma = ["-ffp-contract=fast"] + (["-mfma"] if _cpu_has_fma() else [])
-    return {"strict": _build(cxx, str(base / "strict"), ["-ffp-contract=off"]), "fma": _build(cxx, str(base / "fma"), fma)}
+    flags = {"strict": ["-ffp-contract=off"], "fma": hh.fma_flags()}
+    return {k: HostLib(hh.build(["large_host.cpp", "toy_kernels.cpp"], "libsmfft_large_hostsim.so", str(base / k), f)) for k, f in flags.items()}
 
 
 @pytest.fixture(scope="module")
@@ -176,14 +134,6 @@ def _fp64(name, x):
         return ref.c2r_packed(x)
     x = x.astype(np.complex128)
     return np.fft.ifft(x, axis=1) * n if inverse else np.fft.fft(x, axis=1)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).reshape(-1).view(np.uint32)
-
-
-def _same(a, b):
-    return np.array_equal(_bits(a), _bits(b))
 
 
 def _rows_of(wg, nffts, grid=G):
@@ -285,21 +235,14 @@ def test_host_persistent_loop(host, name):
 
 
 # ---- 4. buffers ------------------------------------------------------------------------------------------------------------------------
-def _guarded(nbytes):
-    """GUARD bytes, 8 more, the data, GUARD bytes; everything a NaN pattern.  -> (words, byte offset of the data)"""
-    words = np.full((2 * GUARD + 8 + nbytes) // 4, GUARD_WORD, dtype=np.uint32)
-    return words, GUARD + 8
-
-
 @pytest.mark.parametrize("name", KERNELS)
 def test_host_guarded_buffers(host, name):
     kind, n, _ = _kind(name)
     for nffts in (NFFTS, 0, 1, G - 1):
         x = _gaussian(name, max(nffts, 1), seed=9)[:nffts]
         nbytes = x.nbytes
-        src, off = _guarded(nbytes)
-        dst, _ = _guarded(nbytes)
-        src[off // 4:(off + nbytes) // 4] = _bits(x)
+        src, off = hh.guarded(x)
+        dst, _ = hh.guarded(nbytes)
         before_src, before_dst = src.copy(), dst.copy()
         rc, msg, bars = host.run_raw(name, src.ctypes.data + off, dst.ctypes.data + off, nffts, guard=GUARD)
         assert rc == 0, f"{name} nFFTs={nffts}: {msg}"
@@ -327,24 +270,13 @@ def test_host_barrier_knock_out(host, name):
     """For every `needed` barrier the run without it differs from the shipped run under some schedule of item 2 -- so item 2 can see a
     missing barrier at that place; for every `redundant` one it is bit-identical under all of them."""
     table = BARRIERS[name]
-    period = len(table)
     x = _gaussian(name, NFFTS)
-    base, bars = host.run(name, x)
-    _assert_barrier_counts(name, bars, NFFTS)
-    order = sorted(SCHEDULES, key=lambda s: s[0] != DESC)       # `descending` first: it is the one that shows most
-    for k, entry in enumerate(table):
-        differs = None
-        for sched, seed, desc in order:
-            got, bars = host.run(name, x, sched=sched, seed=seed, desc=desc, knock_out=k, period=period)
-            _assert_barrier_counts(name, bars, NFFTS)           # a knocked-out barrier is still counted
-            if not _same(got, base):
-                differs = (sched, seed, desc)
-                break
-        print(f"{name} barrier {k}: {'differs under ' + str(differs) if differs else 'bit-identical under all schedules'}")
-        if entry == "needed":
-            assert differs, f"{name}: barrier {k} is entered as needed, but no schedule shows a difference without it"
-        else:
-            assert not differs, f"{name}: barrier {k} is entered as redundant, but schedule {differs} differs without it"
+
+    def run_base():
+        base, bars = host.run(name, x)
+        _assert_barrier_counts(name, bars, NFFTS)
+        return base, bars
+    hh.knock_out(table, run_base, lambda k, sched, seed, desc: host.run(name, x, sched=sched, seed=seed, desc=desc, knock_out=k, period=len(table)), name)
 
 
 # ---- 6. the executor's own checks ----------------------------------------------------------------------------------------------------------

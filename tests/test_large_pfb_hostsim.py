@@ -16,25 +16,21 @@ and 16384 -- against fp64, and whether their barriers are sufficient.
 The host library is built on demand into pytest's temporary directory.  The file's wall time is printed at the end of the module."""
 import ctypes
 import os
-import subprocess
 import sys
 import time
 
 import numpy as np
 import pytest
 
-from tests import test_large_hostsim as lh
+from tests import hostsim_harness as hh
+from tests.hostsim_harness import GUARD, OUT_WORD, guarded as _guarded, rand_complex as _rand
 from tests import test_pfb_gpu as pg
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import large_pfb_model as lpm  # noqa: E402
 
-HOSTSIM = os.path.join(ROOT, "tests", "hostsim")
 SIZES = (8192, 16384)
-GUARD = 4096
-GUARD_WORD = 0x7FC5A5A5    # a NaN of the guards' own
-OUT_WORD = 0xFFFFFFFF      # the NaN the output is prefilled with
 STRIDE, BLOCKED = 1, 2
 # (host grid, kernel schedule, frames per stream of the two streams)
 GRIDS = ((8, STRIDE, 13), (8, BLOCKED, 13), (3, STRIDE, 5))
@@ -52,7 +48,7 @@ class PfbHost:
         lib.hostsim_large_pfb_run.argtypes = [i, i, vp, vp, vp, ll, i, i, i, i, i, ull, i, i, i, lng, ctypes.POINTER(lng), ctypes.POINTER(i)]
         lib.hostsim_large_pfb_last_error.restype = ctypes.c_char_p
 
-    def run(self, n, x, h, power, form=STRIDE, grid=3, sched=lh.ASC, seed=0, desc=0, knock_out=-1, period=0):
+    def run(self, n, x, h, power, form=STRIDE, grid=3, sched=hh.ASC, seed=0, desc=0, knock_out=-1, period=0):
         """-> ((C, F, N) output, barriers per workgroup, (grid, form) as launched); the three buffers sit between guard bands, the
         output NaN-prefilled"""
         C, L = x.shape
@@ -72,42 +68,17 @@ class PfbHost:
         words = C * F * n * (1 if power else 2)
         lo, hi = y0 // 4, y0 // 4 + words
         assert np.array_equal(ys[:lo], before_y[:lo]) and np.array_equal(ys[hi:], before_y[hi:]), "a write outside the output"
-        return ys[lo:hi].view(dtype).reshape(C, F, n).copy(), list(bars)[:launched[0]], tuple(launched)
-
-
-def _guarded(a, fill=None):
-    """GUARD bytes, 8 more, the data, GUARD bytes -> (words, byte offset of the data)"""
-    words = np.full((2 * GUARD + 8 + a.nbytes) // 4, GUARD_WORD, dtype=np.uint32)
-    lo = (GUARD + 8) // 4
-    words[lo:lo + a.nbytes // 4] = lh._bits(a) if fill is None else fill
-    return words, GUARD + 8
+        return hh.payload(ys, y0, (C, F, n), dtype), list(bars)[:launched[0]], tuple(launched)
 
 
 @pytest.fixture(scope="module")
 def host(tmp_path_factory):
     """the build that contracts, as the device does"""
-    cxx = lh._compiler()
-    if cxx is None:
-        pytest.skip("no clang++ that can build the host stub (address_space / ext_vector_type need clang)")
     started = time.time()
     out = str(tmp_path_factory.mktemp("hostsim_large_pfb"))
-    flags = ["-ffp-contract=fast"] + (["-mfma"] if lh._cpu_has_fma() else [])
-    common = [cxx, "-std=c++17", "-O2", "-fPIC", "-I" + HOSTSIM, "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "smfft_amd", "csrc")] + flags
-    objs, procs = [], []
-    for src in ("large_pfb_host.cpp", "hostsim.cpp"):      # hostsim.cpp last: its guard closes the LDS section
-        objs.append(os.path.join(out, src.replace(".cpp", ".o")))
-        procs.append(subprocess.Popen(common + ["-c", os.path.join(HOSTSIM, src), "-o", objs[-1]], stderr=subprocess.PIPE, text=True))
-    for p in procs:
-        err = p.communicate()[1]
-        assert p.returncode == 0, err[-3000:]
-    lib = os.path.join(out, "libsmfft_large_pfb_hostsim.so")
-    subprocess.check_call([cxx, "-shared", "-o", lib] + objs)
+    lib = hh.build(["large_pfb_host.cpp"], "libsmfft_large_pfb_hostsim.so", out, hh.fma_flags(), csrc_includes=True)
     yield PfbHost(lib)
     print(f"\ntests/test_large_pfb_hostsim.py: {time.time() - started:.1f} s of wall time, the build of the host library included")
-
-
-def _rand(rng, shape):
-    return (rng.standard_normal(shape) + 1j * rng.standard_normal(shape)).astype(np.complex64)
 
 
 def _expected_barriers(pairs, grid, form):
@@ -145,7 +116,7 @@ def test_host_filter_bank_matches_fp64(host, n, P, power):
             runs[(grid, form)] = got
     # the blocked form at G = 8 assigns the pairs as the stride form does, so this holds the form's own code path to the same bits, no more
     # (a real permutation: test_host_grids_and_schedules_give_the_same_bits)
-    assert lh._same(runs[(8, STRIDE)], runs[(8, BLOCKED)]), (n, P, power, "stride and blocked schedules differ")
+    assert hh.same(runs[(8, STRIDE)], runs[(8, BLOCKED)]), (n, P, power, "stride and blocked schedules differ")
 
 
 @pytest.mark.parametrize("n", SIZES)
@@ -162,10 +133,10 @@ def test_host_grids_and_schedules_give_the_same_bits(host, n):
         for grid, form in ((3, STRIDE), (8, STRIDE), (8, BLOCKED), (16, STRIDE), (16, BLOCKED)):
             got, bars, launched = host.run(n, x, taps, power, form=form, grid=grid)
             assert launched == (grid, form) and bars == _expected_barriers(18, grid, form)
-            assert lh._same(got, base), (n, power, grid, form)
+            assert hh.same(got, base), (n, power, grid, form)
         # a grid below 8 falls back to the stride form
         got, _, launched = host.run(n, x, taps, power, form=BLOCKED, grid=7)
-        assert launched == (7, STRIDE) and lh._same(got, base)
+        assert launched == (7, STRIDE) and hh.same(got, base)
 
 
 # ---- the case of items 3 and 5: three pairs of two taps -----------------------------------------------------------------------------------
@@ -181,9 +152,9 @@ def test_host_schedule_invariance(host, n):
     x, taps = _small_case(n)
     base, bars, _ = host.run(n, x, taps, False, grid=1)
     assert bars == [18]
-    for sched, seed, desc in lh.SCHEDULES:
+    for sched, seed, desc in hh.SCHEDULES:
         got, b, _ = host.run(n, x, taps, False, grid=2, sched=sched, seed=seed, desc=desc)
-        assert lh._same(got, base), f"N={n}: schedule {sched} seed {seed} workgroups descending={desc} changes the bits"
+        assert hh.same(got, base), f"N={n}: schedule {sched} seed {seed} workgroups descending={desc} changes the bits"
         assert b == [12, 6]
 
 
@@ -197,7 +168,7 @@ def test_host_two_streams_equal_two_launches(host, n):
         together, _, _ = host.run(n, x, taps, power, grid=4)      # pairs straddle the streams in every round
         for c in range(2):
             alone, _, _ = host.run(n, x[c:c + 1], taps, power, grid=2)
-            assert lh._same(alone[0], together[c]), (n, power, c)
+            assert hh.same(alone[0], together[c]), (n, power, c)
 
 
 # ---- 5. barrier knock-out ---------------------------------------------------------------------------------------------------------------------------
@@ -207,16 +178,10 @@ def test_host_barrier_knock_out(host, n):
     image.  For every barrier the run without it differs from the shipped run under some schedule."""
     assert len(BARRIERS) == 6 and all(e == "needed" for e in BARRIERS)
     x, taps = _small_case(n)
-    base, bars, _ = host.run(n, x, taps, False, grid=1)
-    assert bars == [18]
-    order = sorted(lh.SCHEDULES, key=lambda s: s[0] != lh.DESC)
-    for k in range(6):
-        differs = None
-        for sched, seed, desc in order:
-            got, b, _ = host.run(n, x, taps, False, grid=1, sched=sched, seed=seed, desc=desc, knock_out=k, period=6)
-            assert b == bars
-            if not lh._same(got, base):
-                differs = (sched, seed, desc)
-                break
-        print(f"pfb_large<{n}, 0> barrier {k}: {'differs under ' + str(differs) if differs else 'bit-identical under all schedules'}")
-        assert differs, f"pfb_large<{n}, 0>: barrier {k} is entered as needed, but no schedule shows a difference without it"
+
+    def run_base():
+        base, bars, _ = host.run(n, x, taps, False, grid=1)
+        assert bars == [18]
+        return base, bars
+    hh.knock_out(BARRIERS, run_base, lambda k, sched, seed, desc: host.run(n, x, taps, False, grid=1, sched=sched, seed=seed, desc=desc, knock_out=k, period=6)[:2],
+                 f"pfb_large<{n}, 0>")
