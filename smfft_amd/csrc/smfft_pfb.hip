@@ -5,7 +5,7 @@
 // launcher, and once without SMFFT_PFB_N for the C ABI, which only checks and dispatches.
 //
 // The kernel is smfft_pfb_kernel.hpp's pfb_body -- the loop, the schedule, the transform and the store that both filter banks share --
-// with the bank below: per tap the sixteen float coefficients h[p N + u + T c] after the sixteen signal loads, then two fused
+// with the bank of smfft_pfb_bank.hpp (shared with smfft_pfb_spec.hip): per tap the sixteen float coefficients h[p N + u + T c] after the sixteen signal loads, then two fused
 // multiply-adds per element, r[c] = sum_p h[p N + u + T c] x[(f + p) N + u + T c]; nothing between the transform and the store.
 //
 // -DSMFFT_PFB_NT_LOADS=0 / 1: the signal loads plain or non-temporal.  A build variable for the A/B of tools/ab_pfb.py (a second
@@ -30,36 +30,10 @@ struct Host {
 }  // namespace smfft
 
 #ifdef SMFFT_PFB_N
-#include "smfft_pfb_kernel.hpp"
-
-#ifndef SMFFT_PFB_NT_LOADS
-#define SMFFT_PFB_NT_LOADS 1
-#endif
+#include "smfft_pfb_bank.hpp"
 
 namespace smfft {
 namespace pfb {
-
-struct Bank {
-    using Tap = float;
-    static constexpr int kNtLoads = SMFFT_PFB_NT_LOADS;
-    static constexpr bool kPackedNyquist = false;
-    template <int T>
-    static __device__ __forceinline__ void accumulate(float2 (&r)[16], const float2 (&v)[16], const float* __restrict__ hp) {
-        float w[16];
-#pragma unroll
-        for (int q = 0; q < 16; ++q) w[q] = hp[T * q];
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            r[q].x = __builtin_fmaf(w[q], v[q].x, r[q].x);
-            r[q].y = __builtin_fmaf(w[q], v[q].y, r[q].y);
-        }
-    }
-    template <int N>
-    struct Post {
-        __device__ __forceinline__ void init(int) {}
-        __device__ __forceinline__ void apply(float2 (&)[16], float2*, const Engine<N, 0, 1>&) const {}
-    };
-};
 
 template <int N, int POWER>
 __global__ void __launch_bounds__(kPfbThreads) pfb_kernel(const float2* __restrict__ x, const float* __restrict__ h, void* __restrict__ y, PfbPlan plan, long long R) {
