@@ -1,5 +1,6 @@
 """What the ctypes mirrors of the polyphase filter banks share (smfft_amd.pfb: complex streams, smfft_amd.pfb_real: real streams;
-smfft_amd.large_pfb, the complex bank at N = 8192 / 16384, takes the Bank below with its own lengths and its own tuned launch):
+smfft_amd.large_pfb, the complex bank at N = 8192 / 16384, takes the Bank below with its own lengths and its own tuned launch;
+smfft_amd.pfb_spec, the integrated spectra of both, takes one Bank per kind of stream for its checks, prototype and round trip):
 the five entry points' signatures, the calls with their error messages, the prototype and the host-array round trip.  The libraries'
 C ABIs are one for one the same; a bank differs by its prefix, by the samples a frame takes per channel (1: N complex samples, 2: 2N
 real samples) and by the signal's dtype.  The public functions, with the documentation of what each bank computes, are the mirrors'."""
@@ -77,13 +78,16 @@ class Bank:
         m = np.arange(M, dtype=np.float64)
         return (np.sinc((m - (M - 1) / 2) / (self.per_channel * N)) * w).astype(np.float32)
 
-    def channelize(self, x, taps, n_channels, power):
-        """host arrays -> the (C, F, N) rows as the device writes them"""
+    def round_trip(self, x, taps, n_channels, rows, dtype, launch, shape_error, real_error, function, extra=""):
+        """host arrays through one launch: validates x ((C, L) or (L,)) and taps (P N real coefficients, P 2N for real streams), makes them
+        contiguous and copies them in, lets launch(d_signal, L, C, d_taps, N, P, d_output) -> status fill the (C, rows(L, N, P), N) output
+        of `dtype`, prefilled with 0xFF, waits and copies it back.  shape_error, real_error: the caller's ValueError texts; function,
+        extra: its name and its own arguments, for the RuntimeError."""
         x, taps = np.asarray(x), np.asarray(taps)
         if x.ndim not in (1, 2) or taps.ndim != 1:
-            raise ValueError(f"x must be (C, L) or (L,), taps a vector of P {self.chunk} coefficients")
+            raise ValueError(shape_error)
         if np.iscomplexobj(taps) or (self.real and np.iscomplexobj(x)):
-            raise ValueError("the signal and the prototype must be real (complex signals: smfft_amd.pfb)" if self.real else "the prototype must be real")
+            raise ValueError(real_error)
         N = int(n_channels)
         frame = self.per_channel * N
         if N not in self.sizes or taps.size % frame or not 1 <= taps.size // frame <= MAX_TAPS_PER_CHANNEL:
@@ -93,20 +97,27 @@ class Bank:
         x = np.ascontiguousarray(np.atleast_2d(x), dtype=np.float32 if self.real else np.complex64)
         taps = np.ascontiguousarray(taps, dtype=np.float32)
         C, L = x.shape
-        F = self.frames(L, N, P)
-        dtype, width = (np.float32, 4) if power else (np.complex64, 8)
+        F = rows(L, N, P)
         if C * F == 0:
             return np.empty((C, F, N), dtype)
         from . import api      # the device allocator and copies of libsmfft_amd.so
         din, dtaps = api.DeviceBuffer.from_host(x), api.DeviceBuffer.from_host(taps)
-        dout = api.DeviceBuffer(C * F * N * width)
+        dout = api.DeviceBuffer(C * F * N * np.dtype(dtype).itemsize)
         api.lib.smfft_memset(dout.ptr, 0xFF, dout.nbytes)   # NaN pattern: untouched outputs are caught
-        rc = self.call("launch", din.ptr, L, C, dtaps.ptr, N, P, int(bool(power)), dout.ptr, None)
+        rc = launch(din.ptr, L, C, dtaps.ptr, N, P, dout.ptr)
         if rc == 0:
             rc = api.lib.smfft_synchronize()
         if rc != 0:
-            raise RuntimeError(f"{self.name}.channelize(C={C}, L={L}, N={N}, P={P}) -> {rc}")
+            raise RuntimeError(f"{self.name}.{function}(C={C}, L={L}, N={N}, P={P}{extra}) -> {rc}")
         out = dout.to_host(dtype, (C, F, N))
         for b in (din, dtaps, dout):
             b.free()
         return out
+
+    def channelize(self, x, taps, n_channels, power):
+        """host arrays -> the (C, F, N) rows as the device writes them"""
+        return self.round_trip(
+            x, taps, n_channels, self.frames, np.float32 if power else np.complex64,
+            lambda d_signal, L, C, d_taps, N, P, d_output: self.call("launch", d_signal, L, C, d_taps, N, P, int(bool(power)), d_output, None),
+            f"x must be (C, L) or (L,), taps a vector of P {self.chunk} coefficients",
+            "the signal and the prototype must be real (complex signals: smfft_amd.pfb)" if self.real else "the prototype must be real", "channelize")

@@ -212,38 +212,28 @@ int Host<true>::launch<SMFFT_PFB_SPEC_N>(const void* x, const void* h, void* y, 
 }  // namespace smfft
 
 #else  // the C ABI
-#include "smfft_addon_host.hpp"
+#include "smfft_pfb_host.hpp"
 
 namespace {
-// what the eight entry points share.  All validation happens before any HIP call.
+// what the eight entry points share, on the banks' predicates and dispatch (smfft_pfb_host.hpp).  All validation happens before any HIP call.
 template <bool REAL>
 struct SpecApi {
     using Bank = smfft::pfb_spec::Host<REAL>;
-    static bool supported(int N, int P) { return (N == 256 || N == 512 || N == 1024 || N == 2048 || N == 4096) && P >= 1 && P <= 32; }
-    static bool length_ok(long long L) { return L >= 0 && L % Bank::kSamplesPerElement == 0; }
     static smfft::PfbSpecPlan plan_of(long long L, int N, int P, int C, int T) { return smfft::PfbSpecPlan{L / Bank::kSamplesPerElement, N, P, C, T}; }
 
     // -1: an unsupported combination; 0: launch; 1: nothing to do (no whole integration).  No HIP call.
     static int check(long long L, int C, int N, int P, int T, int max_workgroups) {
-        if (!supported(N, P) || T <= 0 || C <= 0 || !length_ok(L) || max_workgroups < 0) return -1;
+        if (!pfb_supported(N, P) || T <= 0 || C <= 0 || !pfb_length_ok<Bank>(L) || max_workgroups < 0) return -1;
         return plan_of(L, N, P, C, T).spectra() == 0 ? 1 : 0;
     }
 
-    static long long spectra(long long L, int N, int P, int T) { return supported(N, P) && T > 0 && length_ok(L) ? plan_of(L, N, P, 1, T).spectra() : -1; }
+    static long long spectra(long long L, int N, int P, int T) { return pfb_supported(N, P) && T > 0 && pfb_length_ok<Bank>(L) ? plan_of(L, N, P, 1, T).spectra() : -1; }
 
     static int dispatch(const void* x, long long L, int C, const void* h, int N, int P, int T, void* y, int max_workgroups, hipStream_t stream) {
         const int cus = compute_units();
         int dev = 0;
         if (cus <= 0 || hipGetDevice(&dev) != hipSuccess) return (int)hipErrorNoDevice;
-        const smfft::PfbSpecPlan plan = plan_of(L, N, P, C, T);
-        switch (N) {
-            case 256: return Bank::template launch<256>(x, h, y, plan, max_workgroups, dev, cus, stream);
-            case 512: return Bank::template launch<512>(x, h, y, plan, max_workgroups, dev, cus, stream);
-            case 1024: return Bank::template launch<1024>(x, h, y, plan, max_workgroups, dev, cus, stream);
-            case 2048: return Bank::template launch<2048>(x, h, y, plan, max_workgroups, dev, cus, stream);
-            case 4096: return Bank::template launch<4096>(x, h, y, plan, max_workgroups, dev, cus, stream);
-        }
-        return -1;
+        return pfb_launch_for<Bank>(N, x, h, y, plan_of(L, N, P, C, T), max_workgroups, dev, cus, stream);
     }
 
     static int launch_tuned(const void* x, long long L, int C, const void* h, int N, int P, int T, void* y, void* hip_stream, int max_workgroups) {

@@ -10,7 +10,7 @@ import ctypes
 
 import numpy as np
 
-from . import _addon, pfb, pfb_real
+from . import _addon, _pfb_bank
 from ._pfb_bank import MAX_TAPS_PER_CHANNEL, SIZES  # noqa: F401
 
 _vp, _i, _ll, _dp = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.POINTER(ctypes.c_double)
@@ -31,6 +31,7 @@ SIGS = {**_sigs(PREFIXES[0]), **_sigs(PREFIXES[1])}
 
 LIB_PATH, load, lib = _addon.loader("libsmfft_pfb_spec.so", "SMFFT_PFB_SPEC_LIB", __name__, SIGS)
 _lib = None
+_banks = tuple(_pfb_bank.Bank("pfb_spec", prefix, lib, real=real) for real, prefix in enumerate(PREFIXES))      # complex streams, real streams
 
 
 def _fn(name, real):
@@ -73,39 +74,15 @@ def benchmark(d_signal, L, n_streams, d_taps, n_channels, taps_per_channel, n_in
 
 def prototype(n_channels, taps_per_channel, window="hamming", real=False):
     """the prototype low-pass of the bank: smfft_amd.pfb.prototype (P N taps), or smfft_amd.pfb_real.prototype (P 2N taps) with real=True"""
-    return (pfb_real if real else pfb).prototype(n_channels, taps_per_channel, window)
+    return _banks[bool(real)].prototype(n_channels, taps_per_channel, window)
 
 
 def integrate(x, taps, n_channels, n_integrate, real=False):
     """x: (C, L) or (L,) signal (complex, or real with real=True), taps: P N (real=True: P 2N) real coefficients (host arrays) ->
     float32 integrated power spectra (C, I, N), I = spectra(L, N, P, n_integrate, real)."""
-    x, taps = np.asarray(x), np.asarray(taps)
-    if x.ndim not in (1, 2) or taps.ndim != 1:
-        raise ValueError("x must be (C, L) or (L,), taps a vector")
-    if np.iscomplexobj(taps) or (real and np.iscomplexobj(x)):
-        raise ValueError("the prototype must be real" + (", and so must the signal with real=True" if real else ""))
-    N, T = int(n_channels), int(n_integrate)
-    frame = (2 if real else 1) * N
-    if N not in SIZES or taps.size % frame or not 1 <= taps.size // frame <= MAX_TAPS_PER_CHANNEL:
-        raise ValueError(f"smfft_amd.pfb_spec serves N in {SIZES} with P {'2N' if real else 'N'} taps, 1 <= P <= {MAX_TAPS_PER_CHANNEL}, "
-                         f"not N = {N} with {taps.size} taps")
-    P = taps.size // frame
-    x = np.ascontiguousarray(np.atleast_2d(x), dtype=np.float32 if real else np.complex64)
-    taps = np.ascontiguousarray(taps, dtype=np.float32)
-    C, L = x.shape
-    n = spectra(L, N, P, T, real)
-    if C * n == 0:
-        return np.empty((C, n, N), np.float32)
-    from . import api      # the device allocator and copies of libsmfft_amd.so
-    din, dtaps = api.DeviceBuffer.from_host(x), api.DeviceBuffer.from_host(taps)
-    dout = api.DeviceBuffer(C * n * N * 4)
-    api.lib.smfft_memset(dout.ptr, 0xFF, dout.nbytes)   # NaN pattern: untouched outputs are caught
-    rc = _fn("launch", real)(din.ptr, L, C, dtaps.ptr, N, P, T, dout.ptr, None)
-    if rc == 0:
-        rc = api.lib.smfft_synchronize()
-    if rc != 0:
-        raise RuntimeError(f"pfb_spec.integrate(C={C}, L={L}, N={N}, P={P}, T={T}, real={bool(real)}) -> {rc}")
-    out = dout.to_host(np.float32, (C, n, N))
-    for b in (din, dtaps, dout):
-        b.free()
-    return out
+    T = int(n_integrate)
+    return _banks[bool(real)].round_trip(
+        x, taps, n_channels, lambda L, N, P: spectra(L, N, P, T, real), np.float32,
+        lambda d_signal, L, C, d_taps, N, P, d_output: _fn("launch", real)(d_signal, L, C, d_taps, N, P, T, d_output, None),
+        "x must be (C, L) or (L,), taps a vector", "the prototype must be real" + (", and so must the signal with real=True" if real else ""),
+        "integrate", f", T={T}, real={bool(real)}")

@@ -27,8 +27,8 @@ _TESTS = [
     ("test_benchmark_adds_to_its_total", lambda n, power: (n, power) == (2048, 0)),
     ("test_channelize_and_prototype_on_two_tones", lambda n, power: n in (256, 1024, 4096)),
 ]
-# every run of the two modules goes through _run: a NaN-fenced signal, a prefilled output and a guard behind it, so the parity grid is
-# the guarded-buffer test of every kernel
+# every run of the two modules goes through the guarded run of tests/pfb_gpu_harness.py: a NaN-fenced signal, a prefilled output and a
+# guard behind it, so the parity grid is the guarded-buffer test of every kernel
 _BOUNDS = [
     ("test_filter_bank_matches_the_model", lambda n, power: True),
     ("test_interior_pointers", lambda n, power: n in (256, 4096)),

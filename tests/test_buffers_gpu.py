@@ -22,8 +22,8 @@ import numpy as np
 import pytest
 
 from oracle import np_reference as ref
-from tests.test_fir_gpu import _check_rows
-from tests.test_fir_gpu import _reference as _fir_reference
+from tests.fir_gpu_harness import _check_rows
+from tests.fir_gpu_harness import _reference as _fir_reference
 
 pytestmark = pytest.mark.gpu
 

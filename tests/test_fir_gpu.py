@@ -10,23 +10,18 @@ by an order of magnitude while every transform is as accurate as anywhere else (
 row's own norm).  So the denominators are max(||y_row||, ||h_k|| ||x_c||) and max(max|y_row|, ||h_k|| max|x_c|): for rows of full
 M-term sums these are the row's own norm and maximum (to within sampling), for rows of partial sums the scale the transforms carry."""
 import ctypes
-import os
-import sys
 
 import numpy as np
 import pytest
 
 from oracle.np_reference import MAX_ABS_TOL, REL_L2_TOL
+from tests.fir_gpu_harness import GUARD, MODES, _check_rows, _rand, _reference, _sampled_windows      # (puts tools/ on the path)
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
 import fir_plan_model as fm  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 SIZES = [256, 512, 1024, 2048, 4096]
-ROW_REL_L2, ROW_MAX = 1e-6, 5e-6
-GUARD = 4096                   # float2 after the output that must stay untouched
-MODES = ("convolve", "correlate")
 
 
 @pytest.fixture(scope="module")
@@ -34,23 +29,6 @@ def sm():
     import smfft_amd
     smfft_amd.FFT_init()
     return smfft_amd
-
-
-def _rand(rng, shape):
-    return (rng.standard_normal(shape) + 1j * rng.standard_normal(shape)).astype(np.complex64)
-
-
-def _reference(x, h, correlate):
-    """fp64 linear convolution / correlation by zero-padded FFTs (exact up to fp64 rounding; checked against np.convolve below)"""
-    x = np.asarray(x, np.complex128)
-    h = np.asarray(h, np.complex128)
-    C, L = x.shape
-    K, M = h.shape
-    g = np.conj(h[:, ::-1]) if correlate else h
-    P = 1 << int(L + M - 1).bit_length()
-    Y = np.fft.ifft(np.fft.fft(x, P)[:, None, :] * np.fft.fft(g, P)[None, :, :], axis=-1)
-    off = M - 1 if correlate else 0
-    return Y[:, :, off:off + L]
 
 
 def _run(sm, x, h, N, mode, spectra=None):
@@ -77,18 +55,6 @@ def _run(sm, x, h, N, mode, spectra=None):
     for b in (dx, dh, dspec, dout):
         b.free()
     return out
-
-
-def _check_rows(got, want, what, x, h):
-    """got, want: (C, K, L'); x: (C, L) the signal the rows were computed from, h: (K, M) the taps"""
-    for c in range(want.shape[0]):
-        xn, xm = np.linalg.norm(x[c]), np.max(np.abs(x[c]))
-        for k in range(want.shape[1]):
-            d = got[c, k].astype(np.complex128) - want[c, k]
-            hn = np.linalg.norm(h[k])
-            l2 = np.linalg.norm(d) / max(np.linalg.norm(want[c, k]), hn * xn, 1e-30)
-            mx = np.max(np.abs(d)) / max(np.max(np.abs(want[c, k])), hn * xm, 1e-30)
-            assert l2 <= ROW_REL_L2 and mx <= ROW_MAX, f"{what} row (c={c}, k={k}): relL2={l2:.3e} maxrel={mx:.3e}"
 
 
 def test_reference_is_numpys_definition():
@@ -291,25 +257,6 @@ def test_grid_stride_loop_with_wrapped_prefetch(sm, N, mode):
     x, h = _rand(rng, (C, L)), _rand(rng, (K, M))
     got = _run(sm, x, h, N, mode)
     _check_rows(got, _reference(x, h, mode == "correlate"), f"grid-stride N={N} {mode}", x, h)
-
-
-def _sampled_windows(sm, dout, x, h, L, starts, mode, what, W):
-    C, K = x.shape[0], h.shape[0]
-    M = h.shape[1]
-    for c in range(C):
-        for k in range(K):
-            hk = h[k].astype(np.complex128)
-            for n0 in starts[c]:
-                got = np.empty(W, np.complex64)
-                assert sm.lib.smfft_memcpy_d2h(got.ctypes.data, dout.ptr + ((c * K + k) * L + n0) * 8, W * 8) == 0
-                if mode == "correlate":
-                    seg = np.r_[x[c, n0:n0 + W + M - 1].astype(np.complex128), np.zeros(max(0, n0 + W + M - 1 - L))]
-                    want = np.correlate(seg, hk, "valid")
-                else:
-                    lo = max(0, n0 - (M - 1))
-                    seg = x[c, lo:n0 + W].astype(np.complex128)
-                    want = np.convolve(seg, hk)[n0 - lo:n0 - lo + W]
-                _check_rows(got[None, None], want[None, None], f"{what} c={c} k={k} n0={n0}", seg[None], hk[None])
 
 
 @pytest.mark.parametrize("mode", MODES)

@@ -11,16 +11,13 @@ import numpy as np
 import pytest
 
 from oracle.np_reference import MAX_ABS_TOL, REL_L2_TOL
-from tests import test_fir_gpu as fg
-from tests.test_fir_gpu import _check_rows, _rand, _reference, _sampled_windows
+from tests.fir_gpu_harness import GUARD, MODES, _check_rows, _rand, _reference, _sampled_windows
 
-import large_fir_model as lfm  # noqa: E402  (tools/ is on the path once tests.test_fir_gpu is imported)
+import large_fir_model as lfm  # noqa: E402  (tools/ is on the path once tests.fir_gpu_harness is imported)
 
 pytestmark = pytest.mark.gpu
 
 SIZES = [8192, 16384]
-GUARD = fg.GUARD
-MODES = fg.MODES
 
 
 @pytest.fixture(scope="module")

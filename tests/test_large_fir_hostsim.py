@@ -3,7 +3,7 @@ tests/hostsim (tests/hostsim/large_fir_host.cpp): the header's own segment loads
 recompute form at N = 8192 and 16384 and the held form at 8192, whichever the library ships -- against fp64, and whether their
 barriers are sufficient.
 
-1. every row against fp64 (`_reference` of tests/test_fir_gpu.py, the tolerances and denominators of its `_check_rows`), on a host
+1. every row against fp64 (`_reference` of tests/fir_gpu_harness.py, the tolerances and denominators of its `_check_rows`), on a host
    grid smaller than the unit count, with a NaN-prefilled output and guard bands around the three buffers;
 2. the prepare kernel against fft(pad(g)) / N;
 3. the same bits under every schedule;
@@ -19,7 +19,7 @@ import numpy as np
 import pytest
 
 from oracle.np_reference import MAX_ABS_TOL, REL_L2_TOL
-from tests import test_fir_gpu as fg
+from tests import fir_gpu_harness as fg
 from tests import hostsim_harness as hh
 from tests.hostsim_harness import GUARD, OUT_WORD, guarded as _guarded, payload as _payload, rand_complex as _rand
 

@@ -380,13 +380,7 @@ def test_every_kernel_is_in_the_inventory_with_its_tests(large_pfb):
 
 
 # ------------------------------------------------------------------------------------------------ leakage
-# (power outside channel 100) / (power in it) of a unit tone at channel 100.37 through the Hamming-windowed sinc of P N taps, from
-# tools/large_pfb_model.py in fp64; the same to three digits at N = 8192 and 16384.  P = 1 is a Hamming-windowed single frame: it leaks
-# more than the rectangular window's 0.60, because its main lobe is twice as wide.
-LEAKAGE = {1: 0.757, 2: 0.325, 3: 0.180, 4: 0.0979, 5: 0.0514, 6: 0.0263, 7: 0.0123, 8: 5.61e-3, 9: 2.13e-3, 10: 7.76e-4, 11: 2.02e-4,
-           12: 3.54e-5, 13: 3.45e-6, 14: 2.43e-6, 15: 4.50e-6, 16: 5.35e-6, 17: 2.49e-6, 18: 1.59e-6, 19: 5.78e-7, 20: 3.79e-7,
-           21: 1.55e-6, 22: 4.12e-7, 23: 2.63e-6, 24: 4.21e-7, 25: 1.21e-6, 26: 5.25e-8, 27: 1.86e-8, 28: 2.39e-7, 29: 1.72e-6,
-           30: 1.03e-6, 31: 2.86e-6, 32: 8.94e-7}
+from tests.pfb_gpu_harness import LEAKAGE  # noqa: E402  (the figures the GPU test holds the device to as well)
 
 
 @pytest.mark.parametrize("N", SIZES)

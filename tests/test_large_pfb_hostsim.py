@@ -2,7 +2,7 @@
 tests/hostsim (tests/hostsim/large_pfb_host.cpp): the header's own tap loop, schedule, transform and stores -- both modes at N = 8192
 and 16384 -- against fp64, and whether their barriers are sufficient.
 
-1. every row against fp64 (tools/large_pfb_model.py, the row bounds of tests/test_pfb_gpu.py: complex ||d||_2 / (sqrt(N) ||s||_2) <= 1e-6
+1. every row against fp64 (tools/large_pfb_model.py, the row bounds of tests/pfb_gpu_harness.py: complex ||d||_2 / (sqrt(N) ||s||_2) <= 1e-6
    and max <= 5e-6, power L1 <= 2e-6 and max <= 1e-5), with a NaN-prefilled output and guard bands around the three buffers.  Shapes:
    P in {1, 3}, two streams, three full rounds of the grid and a ragged one -- 26 pairs on a host grid of 8 under both schedules
    (two streams make the pair count even: 3 G + 2), 10 pairs on a grid of 3 under the stride schedule (3 G + 1; the blocked form needs
@@ -23,8 +23,8 @@ import numpy as np
 import pytest
 
 from tests import hostsim_harness as hh
+from tests import pfb_gpu_harness as gh
 from tests.hostsim_harness import GUARD, OUT_WORD, guarded as _guarded, rand_complex as _rand
-from tests import test_pfb_gpu as pg
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -39,6 +39,7 @@ GRIDS = ((8, STRIDE, 13), (8, BLOCKED, 13), (3, STRIDE, 5))
 # transforms touches no LDS, so the sixth still separates read_c (thread u reads u + T*i) from the next pair's write of exchange A
 # (thread u writes q*SA + u: other threads' slots).
 BARRIERS = ["needed"] * 6
+BANK = gh.Bank("large_pfb")      # the bank's row checks; the library itself is not loaded here
 
 
 class PfbHost:
@@ -109,10 +110,7 @@ def test_host_filter_bank_matches_fp64(host, n, P, power):
             assert launched == (grid, form) and bars == _expected_barriers(pairs, grid, form), (n, P, grid, form, bars)
             assert np.isfinite(got.view(np.float32)).all(), "outputs left unwritten"
             what = f"host N={n} P={P} grid={grid} schedule={form}"
-            if power:
-                pg._check_power(got, ref.real ** 2 + ref.imag ** 2, what + " power")
-            else:
-                pg._check_complex(got, ref, s, what)
+            BANK.check(got, ref, s, power, what + (" power" if power else ""))
             runs[(grid, form)] = got
     # the blocked form at G = 8 assigns the pairs as the stride form does, so this holds the form's own code path to the same bits, no more
     # (a real permutation: test_host_grids_and_schedules_give_the_same_bits)

@@ -1,6 +1,6 @@
 """The two polyphase filter banks (libsmfft_pfb.so, libsmfft_pfb_real.so) per output element and in isolation, on an MI355X: the twenty
-kernels of tests/pfb_inventory.py through one set of tests, parametrized by bank.  Every run goes through the harness of the bank's own
-GPU module (tests/test_pfb_gpu.py, tests/test_pfb_real_gpu.py: _run, a NaN-fenced signal into a prefilled, guarded output).
+kernels of tests/pfb_inventory.py through one set of tests, parametrized by bank.  Every run goes through the guarded run of
+tests/pfb_gpu_harness.py (Bank.run: a NaN-fenced signal into a prefilled, guarded output).
 A test is one bank (the probe: one bank and length); its shapes, modes and cases are loops inside it, every failure message names its own,
 so that the module adds eighteen tests to the GPU suite, not ninety.
 
@@ -30,7 +30,7 @@ B3  Non-finite values reach exactly their frames (test_nan_sample_reaches_exactl
     or a +Inf at one sample of chunk j of stream c makes every element of frames max(0, j - P + 1) ... min(j, F - 1) of that stream
     non-finite and leaves every other output word as the clean run wrote it -- the first chunk, the last chunk of the first window, an
     interior one and the last chunk a stream reads (the next stream's frame 0 stays clean; in the last stream the clamped slots of the
-    ragged last tile load the poisoned pair again and must store nothing: the guard of _run); a NaN tap makes every element of every
+    ragged last tile load the poisoned pair again and must store nothing: the guard of the run); a NaN tap makes every element of every
     frame non-finite.  NaN is data here: nothing faults."""
 import json
 import os
@@ -38,12 +38,10 @@ import os
 import numpy as np
 import pytest
 
+from tests import pfb_gpu_harness as gh
 from tests import pfb_probe_cases as ppc
 from tests import probe_cases as pc
-from tests import test_pfb_gpu as tc
-from tests import test_pfb_real_gpu as tr
-
-pm, prm = tc.pm, tr.prm
+from tests.pfb_gpu_harness import bits as _bits
 
 pytestmark = pytest.mark.gpu
 
@@ -53,55 +51,8 @@ SLICE = 1 << 22                # output elements per slice of A1's expected rows
 STREAM_SCALES = (-40, -13, 11, 40)
 TAP_SCALES = (-7, 5)
 
-
-class Bank:
-    """one of the two libraries behind the calls the tests need"""
-
-    def __init__(self, name):
-        self.name, self.real = name, name == "pfb_real"
-        self.mod = tr if self.real else tc
-
-    @property
-    def lib(self):
-        if self.real:
-            from smfft_amd import pfb_real as m
-        else:
-            from smfft_amd import pfb as m
-        m.lib()
-        return m
-
-    def chunk(self, N):
-        """samples per chunk: the hop, and the transform's length"""
-        return 2 * N if self.real else N
-
-    def rand(self, rng, shape):
-        return self.mod._rand(rng, shape)
-
-    def taps(self, rng, N, P):
-        return rng.standard_normal(P * self.chunk(N)).astype(np.float32)
-
-    def run(self, sm, x, h, N, power, R=None, finite=True):
-        lib = self.lib
-        launcher = None if R is None else (lambda *a: lib.launch_tuned(*a[:-1], R, power=a[-1]))
-        return self.mod._run(sm, lib, x, h, N, power, launcher=launcher, finite=finite)
-
-    def check_rows(self, got, x, h, N, power, what):
-        """the bank's own row checks against its fp64 model"""
-        if self.real:
-            ref = prm.pfb_real(x, h, N)
-            if power:
-                tr._check_power(got, ref, what)
-            else:
-                tr._check_complex(got, ref, prm.scale(x, h, N), what)
-        else:
-            ref = pm.pfb(x, h, N)
-            if power:
-                tc._check_power(got, ref.real ** 2 + ref.imag ** 2, what)
-            else:
-                tc._check_complex(got, ref, pm.scale(x, h, N), what)
-
-
-BANKS = {name: Bank(name) for name in ("pfb", "pfb_real")}
+BANKS = {name: gh.Bank(name) for name in ("pfb", "pfb_real")}
+pm = BANKS["pfb"].model
 
 
 @pytest.fixture(scope="module")
@@ -121,10 +72,6 @@ def bank(request):
 def ratchet():
     with open(RATCHET) as f:
         return json.load(f)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def _non_finite(out):
@@ -210,7 +157,7 @@ def _equal_windows(sm, bank, N, P, power):
     stream = np.concatenate([np.tile(period, -(-chunks // Q))[:chunks * W], bank.rand(rng, (6,))])      # + an unread tail
     x, h = np.tile(stream, (C, 1)), bank.taps(rng, N, P)
     for R in (1, 4):
-        out = bank.run(sm, x, h, N, power, R=R)
+        out = bank.run(sm, x, h, N, power, launcher=bank.tuned(R))
         assert out.shape == (C, F, N)
         bits = _bits(out).reshape(C, F, -1)
         for cls in range(Q):
@@ -294,7 +241,7 @@ def test_nan_tap_reaches_every_frame(sm, bank):
 
 def _nan_tap(sm, bank, N, P, power):
     rng, C, F, x, h = _nan_inputs(bank, N, P)
-    bank.run(sm, x, h, N, power)                       # the clean run is finite and writes every element (_run)
+    bank.run(sm, x, h, N, power)                       # the clean run is finite and writes every element (the guarded run)
     for t in (0, int(rng.integers(h.size)), h.size - 1):
         dirty_h = h.copy()
         dirty_h[t] = np.nan
