@@ -12,6 +12,8 @@ import os
 
 import numpy as np
 
+from . import _fir_bank
+
 NREUSES = 100
 LIB_PATH = os.environ.get("SMFFT_AMD_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libsmfft_amd.so")
 
@@ -44,9 +46,7 @@ _SIGS = {
     "smfft_ct_dif_external_benchmark": (_i, [_vp, _vp, _i, _i, _i, _dp]),
     "smfft_ct_dif_launch": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "smfft_copy_launch": (_i, [_vp, _vp, ctypes.c_longlong, _vp]),
-    "smfft_fir_prepare": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
-    "smfft_fir_launch": (_i, [_vp, ctypes.c_longlong, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "smfft_fir_benchmark": (_i, [_vp, ctypes.c_longlong, _i, _vp, _i, _i, _i, _i, _vp, _dp]),
+    **_fir_bank.sigs("smfft_fir"),
     "smfft_gpu_ct": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _dp, _dp]),
     "smfft_gpu_st": (_i, [_vp, _vp, _i, _i, _i, _dp, _dp]),
     "smfft_gpu_r2c": (_i, [_vp, _vp, _i, _i, _i]),
@@ -213,36 +213,25 @@ def launch_dif(d_in, d_out, N, nFFTs, inverse=False, stream=0):
         raise RuntimeError(f"smfft_ct_dif_launch(N={N}) -> {rc}")
 
 
-_FIR_MODES = {"convolve": 0, "correlate": 1}
-
-
-def _fir_mode(mode):
-    if mode not in _FIR_MODES:
-        raise ValueError(f"mode must be 'convolve' or 'correlate', not {mode!r}")
-    return _FIR_MODES[mode]
+# the FIR filter banks of the main library: this module's already loaded lib (smfft_amd.fir_real and smfft_amd.large_fir are the other banks)
+_fir = _fir_bank.Bank("", "smfft_fir", lambda: lib, (256, 512, 1024, 2048, 4096), real=False, refuses=False)
 
 
 def fir_prepare(d_taps, d_spectra, n_taps, n_filters, N, mode="convolve", stream=0):
     """Filter spectra for fir_launch, launch only: d_spectra[k*N + j] = DFT_N(pad_N(g_k))[j] / N, g_k = h_k (convolve) or
     conj(h_k[::-1]) (correlate), from d_taps = n_filters x n_taps complex64 (smfft_fir_prepare)."""
-    rc = lib.smfft_fir_prepare(d_taps, n_taps, n_filters, N, _fir_mode(mode), d_spectra, stream)
-    if rc != 0:
-        raise RuntimeError(f"smfft_fir_prepare(M={n_taps}, K={n_filters}, N={N}) -> {rc}")
+    _fir.prepare(d_taps, d_spectra, n_taps, n_filters, N, mode, stream)
 
 
 def fir_launch(d_signal, L, n_channels, d_spectra, n_filters, n_taps, N, d_output, mode="convolve", stream=0):
     """Overlap-save filter bank, launch only (no events, no sync): d_output[(c*K + k)*L + n] = np.convolve(x_c, h_k)[n] (convolve) or
     np.correlate(np.r_[x_c, zeros(M-1)], h_k, 'valid')[n] (correlate), with spectra of fir_prepare in the same mode (smfft_fir_launch)."""
-    rc = lib.smfft_fir_launch(d_signal, L, n_channels, d_spectra, n_filters, n_taps, N, _fir_mode(mode), d_output, stream)
-    if rc != 0:
-        raise RuntimeError(f"smfft_fir_launch(L={L}, C={n_channels}, K={n_filters}, M={n_taps}, N={N}) -> {rc}")
+    _fir.launch(d_signal, L, n_channels, d_spectra, n_filters, n_taps, N, d_output, mode, stream)
 
 
 def fir_fft_size(n_taps):
     """The transform length fir() picks for n_taps taps: the next power of two >= 4 M, clamped to 256 ... 4096."""
-    if not 1 <= n_taps < 4096:
-        raise ValueError(f"n_taps = {n_taps}: the filter banks take 1 ... 4095 taps")
-    return min(4096, max(256, 1 << (4 * n_taps - 1).bit_length()))
+    return _fir.fir_fft_size(n_taps)
 
 
 # ---- NumPy-level conveniences used by the tests (host arrays in/out, still the HIP path) -----------
@@ -285,26 +274,7 @@ def fir(x, taps, mode="convolve", fft_size=None):
     """x: (C, L) or (L,) signal, taps: (K, M) or (M,) filters (host arrays; real ones are cast to complex64) -> (C, K, L) complex64:
     out[c, k] = np.convolve(x[c], taps[k])[:L] (mode="convolve") or np.correlate(np.r_[x[c], zeros(M-1)], taps[k], 'valid')
     (mode="correlate"), through the overlap-save kernel with N = fft_size (None: fir_fft_size(M))."""
-    corr = _fir_mode(mode)
-    x, taps = np.asarray(x), np.asarray(taps)
-    if x.ndim not in (1, 2) or taps.ndim not in (1, 2):
-        raise ValueError("x must be (C, L) or (L,), taps (K, M) or (M,)")
-    x = np.ascontiguousarray(np.atleast_2d(x), dtype=np.complex64)
-    taps = np.ascontiguousarray(np.atleast_2d(taps), dtype=np.complex64)
-    (C, L), (K, M) = x.shape, taps.shape
-    N = fir_fft_size(M) if fft_size is None else int(fft_size)
-    din, dtaps = DeviceBuffer.from_host(x), DeviceBuffer.from_host(taps)
-    dspec = DeviceBuffer(max(K * N * 8, 8))
-    dout = DeviceBuffer(max(C * K * L * 8, 8))
-    lib.smfft_memset(dout.ptr, 0xFF, dout.nbytes)   # NaN pattern: untouched outputs are caught
-    rc = lib.smfft_fir_prepare(dtaps.ptr, M, K, N, corr, dspec.ptr, None)
-    if rc == 0:
-        rc = lib.smfft_fir_launch(din.ptr, L, C, dspec.ptr, K, M, N, corr, dout.ptr, None)
-    if rc == 0:
-        rc = lib.smfft_synchronize()
-    if rc != 0:
-        raise RuntimeError(f"fir(C={C}, L={L}, K={K}, M={M}, N={N}, {mode}) -> {rc}")
-    return dout.to_host(np.complex64, (C, K, L))
+    return _fir.fir(x, taps, mode, fft_size)
 
 
 def stockham_c2c(x, inverse=True):

@@ -8,19 +8,16 @@
 // a product with the filter's spectrum, one inverse transform and the predicated store of the segment's valid window.  Every output
 // element is written once; nothing but the signal, the spectra (L2-resident) and the outputs touches memory.
 // The segmentation (load start, store window, output index) is smfft_fir.hpp's FirWindow, shared with the host and the CPU test.
+// The launch constants and the launchers are smfft_fir_kernel.hpp's, shared with the real bank (smfft_fir_real.hip); the checks, the
+// dispatch over the lengths and the bodies of the three entry points are smfft_fir_host.hpp's, shared with all three banks.
 #include <hip/hip_runtime.h>
 
-#include "smfft/smfft_engine.hpp"
-#include "smfft_fir.hpp"
-#include "smfft_host_util.hpp"
+#include "smfft_fir_kernel.hpp"
+#include "smfft_fir_host.hpp"
 #include "../../include/smfft.h"
 
 namespace smfft {
 namespace {
-
-constexpr int kFirThreads = 256;
-constexpr int kFirGridCap = 12288;       // workgroups along the segment tiles (grid-strided beyond), as the external kernels
-constexpr int kFirTargetWorkgroups = 2048;  // the filter-group rule's target: twice the workgroups the chip holds at once
 
 template <int N>
 __global__ void __launch_bounds__(kFirThreads) fir_overlap_save_kernel(const float2* __restrict__ x, const float2* __restrict__ H, float2* __restrict__ y,
@@ -107,81 +104,33 @@ __global__ void __launch_bounds__(kFirThreads) fir_prepare_kernel(const float2* 
     }
 }
 
-bool fir_size_ok(int N) { return N == 256 || N == 512 || N == 1024 || N == 2048 || N == 4096; }
-
-template <int N>
-int launch_fir_prepare_n(const float2* taps, int M, int K, int correlate, float2* spectra, hipStream_t st) {
-    constexpr int F = Geometry<N>::kFftsPerBlock;
-    fir_prepare_kernel<N><<<(K + F - 1) / F, kFirThreads, 0, st>>>(taps, M, K, correlate, spectra);
-    return (int)hipGetLastError();
-}
-
-template <int N>
-int launch_fir_n(const float2* x, const FirWindow& w, int C, const float2* H, int K, float2* y, hipStream_t st) {
-    const long long tiles = (w.segments() * C + Geometry<N>::kFftsPerBlock - 1) / Geometry<N>::kFftsPerBlock;
-    const int group = fir_filter_group_size(tiles, K, kFirTargetWorkgroups);
-    const dim3 grid((unsigned)(tiles < kFirGridCap ? tiles : kFirGridCap), (unsigned)((K + group - 1) / group));
-    fir_overlap_save_kernel<N><<<grid, kFirThreads, 0, st>>>(x, H, y, w, C, K, group);
-    return (int)hipGetLastError();
-}
-
-int dispatch_fir(const void* x, long long L, int C, const void* H, int K, int M, int N, int correlate, void* y, hipStream_t st) {
-    const FirWindow w{L, N, M, correlate != 0};
-    const float2* xs = (const float2*)x;
-    const float2* hs = (const float2*)H;
-    float2* ys = (float2*)y;
-    switch (N) {
-        case 256: return launch_fir_n<256>(xs, w, C, hs, K, ys, st);
-        case 512: return launch_fir_n<512>(xs, w, C, hs, K, ys, st);
-        case 1024: return launch_fir_n<1024>(xs, w, C, hs, K, ys, st);
-        case 2048: return launch_fir_n<2048>(xs, w, C, hs, K, ys, st);
-        case 4096: return launch_fir_n<4096>(xs, w, C, hs, K, ys, st);
+// the bank of smfft_fir_host.hpp
+struct Bank {
+    using Sizes = FirSizes<256, 512, 1024, 2048, 4096>;
+    template <int N>
+    static int launch(const void* x, const FirWindow& w, int C, const void* H, int K, void* y, hipStream_t stream) {
+        return fir_launch<N>(fir_overlap_save_kernel<N>, (const float2*)x, w, w.segments(), C, (const float2*)H, K, (float2*)y, stream);
     }
-    return -1;
-}
-
-// -1: an unsupported combination; 0: launch; 1: nothing to do (an empty signal).  No HIP call.
-int fir_check(long long L, int C, int K, int M, int N) {
-    if (!fir_size_ok(N) || M < 1 || M >= N || C <= 0 || K <= 0 || L < 0) return -1;
-    return L == 0 ? 1 : 0;
-}
+    template <int N>
+    static int launch_prepare(const void* taps, int M, int K, int correlate, void* spectra, hipStream_t stream) {
+        return fir_launch_prepare<N>(fir_prepare_kernel<N>, (const float2*)taps, M, K, correlate, (float2*)spectra, stream);
+    }
+};
+using Api = FirApi<Bank>;
 
 }  // namespace
 }  // namespace smfft
 
 extern "C" int smfft_fir_prepare(const void* d_taps, int n_taps, int n_filters, int FFT_size, int correlate, void* d_spectra, void* hip_stream) {
-    using namespace smfft;
-    if (!fir_size_ok(FFT_size) || n_taps < 1 || n_taps >= FFT_size || n_filters <= 0) return -1;
-    const float2* t = (const float2*)d_taps;
-    float2* o = (float2*)d_spectra;
-    const hipStream_t st = (hipStream_t)hip_stream;
-    const int c = correlate != 0;
-    switch (FFT_size) {
-        case 256: return launch_fir_prepare_n<256>(t, n_taps, n_filters, c, o, st);
-        case 512: return launch_fir_prepare_n<512>(t, n_taps, n_filters, c, o, st);
-        case 1024: return launch_fir_prepare_n<1024>(t, n_taps, n_filters, c, o, st);
-        case 2048: return launch_fir_prepare_n<2048>(t, n_taps, n_filters, c, o, st);
-        case 4096: return launch_fir_prepare_n<4096>(t, n_taps, n_filters, c, o, st);
-    }
-    return -1;
+    return smfft::Api::prepare(d_taps, n_taps, n_filters, FFT_size, correlate, d_spectra, hip_stream);
 }
 
 extern "C" int smfft_fir_launch(const void* d_signal, long long signal_length, int n_channels, const void* d_spectra, int n_filters, int n_taps,
                                 int FFT_size, int correlate, void* d_output, void* hip_stream) {
-    const int chk = smfft::fir_check(signal_length, n_channels, n_filters, n_taps, FFT_size);
-    if (chk != 0) return chk < 0 ? -1 : 0;
-    return smfft::dispatch_fir(d_signal, signal_length, n_channels, d_spectra, n_filters, n_taps, FFT_size, correlate, d_output, (hipStream_t)hip_stream);
+    return smfft::Api::launch(d_signal, signal_length, n_channels, d_spectra, n_filters, n_taps, FFT_size, correlate, d_output, hip_stream);
 }
 
 extern "C" int smfft_fir_benchmark(const void* d_signal, long long signal_length, int n_channels, const void* d_spectra, int n_filters, int n_taps,
                                    int FFT_size, int correlate, void* d_output, double* FFT_time) {
-    const int chk = smfft::fir_check(signal_length, n_channels, n_filters, n_taps, FFT_size);
-    if (chk != 0) return chk < 0 ? -1 : 0;
-    GpuTimer timer;
-    timer.Start();
-    const int rc = smfft::dispatch_fir(d_signal, signal_length, n_channels, d_spectra, n_filters, n_taps, FFT_size, correlate, d_output, 0);
-    timer.Stop();
-    const float ms = timer.Elapsed();
-    if (rc == 0 && FFT_time) *FFT_time += ms;
-    return rc;
+    return smfft::Api::benchmark(d_signal, signal_length, n_channels, d_spectra, n_filters, n_taps, FFT_size, correlate, d_output, FFT_time);
 }

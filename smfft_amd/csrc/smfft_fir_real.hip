@@ -2,13 +2,13 @@
 // the C ABI of include/smfft_fir_real.h.
 //
 // Compiled once per length (Makefile: -DSMFFT_FIR_REAL_N=256 ... 4096, flags of their own: FIR_REAL_FLAGS_<N>) for the two kernels
-// and their launchers, and once without SMFFT_FIR_REAL_N for the C ABI, which only checks and dispatches.
+// and their launchers, and once without SMFFT_FIR_REAL_N for the C ABI, which only checks and dispatches (smfft_fir_host.hpp).
 //
-// The kernel is smfft_fir.hip's fir_overlap_save_kernel with another load and another store.  For a real filter
-// g, conv(x1 + i x2, g) = conv(x1, g) + i conv(x2, g): two consecutive real segments of a channel go into the real and the imaginary
-// lane of one complex transform of the register engine, the product with the filter's ordinary N-point spectrum and the inverse
-// transform are those of the complex bank, and the two filtered segments come out in .x and .y.  No Hermitian split or merge, no new
-// transform code.  The pairing (pairs per channel, the absent partner of an odd segment count, load starts, store windows) is
+// The kernel is smfft_fir.hip's fir_overlap_save_kernel with another load and another store (the launch constants
+// and the launchers are smfft_fir_kernel.hpp's, which also says why the two bodies are written out twice).  For a real filter g,
+// conv(x1 + i x2, g) = conv(x1, g) + i conv(x2, g): two consecutive real segments of a channel go into the real and the imaginary lane of one complex transform of the register engine, the product with the filter's ordinary N-point spectrum and the
+// inverse transform are those of the complex bank, and the two filtered segments come out in .x and .y.  No Hermitian split or merge,
+// no new transform code.  The pairing (pairs per channel, the absent partner of an odd segment count, load starts, store windows) is
 // smfft_fir_real.hpp's FirPairs, shared with the host and the CPU test.
 //
 // -DSMFFT_FIR_REAL_NT_LOADS=0 / 1: the signal loads plain or non-temporal.  A build variable for the A/B of tools/ab_fir_real.py (a
@@ -30,7 +30,7 @@ int launch_prepare(const float* taps, int M, int K, int correlate, float2* spect
 }  // namespace smfft
 
 #ifdef SMFFT_FIR_REAL_N
-#include "smfft/smfft_engine.hpp"
+#include "smfft_fir_kernel.hpp"
 
 #ifndef SMFFT_FIR_REAL_NT_LOADS
 #define SMFFT_FIR_REAL_NT_LOADS 1
@@ -38,10 +38,6 @@ int launch_prepare(const float* taps, int M, int K, int correlate, float2* spect
 
 namespace smfft {
 namespace fir_real {
-
-constexpr int kFirThreads = 256;
-constexpr int kFirGridCap = 12288;          // workgroups along the pair tiles (grid-strided beyond), as smfft_fir.hip
-constexpr int kFirTargetWorkgroups = 2048;  // the filter-group rule's target, as smfft_fir.hip
 
 // the float forms of the engine's gload / gstore: one dword per lane, vector memory instructions only
 __device__ __forceinline__ float gload(const float* p) {
@@ -156,84 +152,49 @@ __global__ void __launch_bounds__(kFirThreads) fir_real_prepare_kernel(const flo
 
 template <>
 int launch<SMFFT_FIR_REAL_N>(const float* x, const FirPairs& fp, int C, const float2* H, int K, float* y, hipStream_t stream) {
-    constexpr int N = SMFFT_FIR_REAL_N, F = Geometry<N>::kFftsPerBlock;
-    const long long tiles = (fp.pairs() * C + F - 1) / F;
-    const int group = fir_filter_group_size(tiles, K, kFirTargetWorkgroups);
-    const dim3 grid((unsigned)(tiles < kFirGridCap ? tiles : kFirGridCap), (unsigned)((K + group - 1) / group));
-    fir_real_overlap_save_kernel<N><<<grid, kFirThreads, 0, stream>>>(x, H, y, fp, C, K, group);
-    return (int)hipGetLastError();
+    return fir_launch<SMFFT_FIR_REAL_N>(fir_real_overlap_save_kernel<SMFFT_FIR_REAL_N>, x, fp, fp.pairs(), C, H, K, y, stream);
 }
 
 template <>
 int launch_prepare<SMFFT_FIR_REAL_N>(const float* taps, int M, int K, int correlate, float2* spectra, hipStream_t stream) {
-    constexpr int N = SMFFT_FIR_REAL_N, F = Geometry<N>::kFftsPerBlock;
-    fir_real_prepare_kernel<N><<<(K + F - 1) / F, kFirThreads, 0, stream>>>(taps, M, K, correlate, spectra);
-    return (int)hipGetLastError();
+    return fir_launch_prepare<SMFFT_FIR_REAL_N>(fir_real_prepare_kernel<SMFFT_FIR_REAL_N>, taps, M, K, correlate, spectra, stream);
 }
 
 }  // namespace fir_real
 }  // namespace smfft
 
 #else  // the C ABI
-#include "smfft_addon_host.hpp"
+#include "smfft_fir_host.hpp"
 
 namespace {
-bool supported(int N) { return N == 256 || N == 512 || N == 1024 || N == 2048 || N == 4096; }
-
-// -1: an unsupported combination; 0: launch; 1: nothing to do (an empty signal).  No HIP call.
-int check(long long L, int C, int K, int M, int N) {
-    if (!supported(N) || M < 1 || M >= N || C <= 0 || K <= 0 || L < 0) return -1;
-    return L == 0 ? 1 : 0;
-}
-
-int dispatch(const void* x, long long L, int C, const void* H, int K, int M, int N, int correlate, void* y, hipStream_t stream) {
-    using namespace smfft::fir_real;
-    const smfft::FirPairs fp{smfft::FirWindow{L, N, M, correlate != 0}};
-    const float* xs = (const float*)x;
-    const float2* hs = (const float2*)H;
-    float* ys = (float*)y;
-    switch (N) {
-        case 256: return launch<256>(xs, fp, C, hs, K, ys, stream);
-        case 512: return launch<512>(xs, fp, C, hs, K, ys, stream);
-        case 1024: return launch<1024>(xs, fp, C, hs, K, ys, stream);
-        case 2048: return launch<2048>(xs, fp, C, hs, K, ys, stream);
-        case 4096: return launch<4096>(xs, fp, C, hs, K, ys, stream);
+struct Bank {
+    using Sizes = FirSizes<256, 512, 1024, 2048, 4096>;
+    template <int N>
+    static int launch(const void* x, const smfft::FirWindow& w, int C, const void* H, int K, void* y, hipStream_t stream) {
+        return smfft::fir_real::launch<N>((const float*)x, smfft::FirPairs{w}, C, (const float2*)H, K, (float*)y, stream);
     }
-    return -1;
-}
+    template <int N>
+    static int launch_prepare(const void* taps, int M, int K, int correlate, void* spectra, hipStream_t stream) {
+        return smfft::fir_real::launch_prepare<N>((const float*)taps, M, K, correlate, (float2*)spectra, stream);
+    }
+};
+using Api = FirApi<Bank>;
 }  // namespace
 
 extern "C" {
 
 int smfft_fir_real_prepare(const void* d_taps, int n_taps, int n_filters, int FFT_size, int correlate, void* d_spectra, void* hip_stream) {
-    using namespace smfft::fir_real;
-    if (!supported(FFT_size) || n_taps < 1 || n_taps >= FFT_size || n_filters <= 0) return -1;
-    const float* t = (const float*)d_taps;
-    float2* o = (float2*)d_spectra;
-    const hipStream_t st = (hipStream_t)hip_stream;
-    const int c = correlate != 0;
-    switch (FFT_size) {
-        case 256: return launch_prepare<256>(t, n_taps, n_filters, c, o, st);
-        case 512: return launch_prepare<512>(t, n_taps, n_filters, c, o, st);
-        case 1024: return launch_prepare<1024>(t, n_taps, n_filters, c, o, st);
-        case 2048: return launch_prepare<2048>(t, n_taps, n_filters, c, o, st);
-        case 4096: return launch_prepare<4096>(t, n_taps, n_filters, c, o, st);
-    }
-    return -1;
+    return Api::prepare(d_taps, n_taps, n_filters, FFT_size, correlate, d_spectra, hip_stream);
 }
 
 int smfft_fir_real_launch(const void* d_signal, long long signal_length, int n_channels, const void* d_spectra, int n_filters, int n_taps,
                           int FFT_size, int correlate, void* d_output, void* hip_stream) {
-    const int chk = check(signal_length, n_channels, n_filters, n_taps, FFT_size);
-    if (chk != 0) return chk < 0 ? -1 : 0;
-    return dispatch(d_signal, signal_length, n_channels, d_spectra, n_filters, n_taps, FFT_size, correlate, d_output, (hipStream_t)hip_stream);
+    return Api::launch(d_signal, signal_length, n_channels, d_spectra, n_filters, n_taps, FFT_size, correlate, d_output, hip_stream);
 }
 
 int smfft_fir_real_benchmark(const void* d_signal, long long signal_length, int n_channels, const void* d_spectra, int n_filters, int n_taps,
                              int FFT_size, int correlate, void* d_output, double* FFT_time) {
-    const int chk = check(signal_length, n_channels, n_filters, n_taps, FFT_size);
-    if (chk != 0) return chk < 0 ? -1 : 0;
-    return timed_launch(FFT_time, [&] { return dispatch(d_signal, signal_length, n_channels, d_spectra, n_filters, n_taps, FFT_size, correlate, d_output, nullptr); });
+    return Api::benchmark(d_signal, signal_length, n_channels, d_spectra, n_filters, n_taps, FFT_size, correlate, d_output, FFT_time);
 }
 
 }  // extern "C"

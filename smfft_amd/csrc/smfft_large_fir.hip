@@ -3,7 +3,7 @@
 //
 // Compiled three times (Makefile): -DSMFFT_LARGE_FIR_N=8192 and -DSMFFT_LARGE_FIR_N=16384 give one object per length with its kernels
 // and its launchers (flags of their own: LARGE_FIR_FLAGS_<N>); without SMFFT_LARGE_FIR_N it is the C ABI, which only checks and
-// dispatches.
+// dispatches (smfft_fir_host.hpp, shared with the banks at N = 256 ... 4096).
 //
 // The work split (include/smfft/smfft_large_fir.hpp has the two forms of the filter loop; DESIGN.md section 11 the measurement that
 // chose between them).  cus = the compute units of the device.
@@ -72,49 +72,41 @@ int launch_fir_prepare<SMFFT_LARGE_FIR_N>(const float2* taps, int M, int K, int 
 }  // namespace smfft
 
 #else  // the C ABI
-#include "smfft_addon_host.hpp"
+#include "smfft_fir_host.hpp"
 
 namespace {
-bool supported(int FFT_size) { return FFT_size == 8192 || FFT_size == 16384; }
-
-// -1: an unsupported combination; 0: launch; 1: nothing to do (an empty signal).  No HIP call.
-int check(long long L, int C, int K, int M, int N) {
-    if (!supported(N) || M < 1 || M >= N || C <= 0 || K <= 0 || L < 0) return -1;
-    return L == 0 ? 1 : 0;
-}
-
-int dispatch(const void* x, long long L, int C, const void* H, int K, int M, int N, int correlate, void* y, hipStream_t stream) {
-    const int cus = compute_units();
-    if (cus <= 0) return (int)hipErrorNoDevice;
-    const smfft::FirWindow w{L, N, M, correlate != 0};
-    if (N == 8192) return smfft::large::launch_fir<8192>((const float2*)x, (const float2*)H, (float2*)y, w, C, K, cus, stream);
-    return smfft::large::launch_fir<16384>((const float2*)x, (const float2*)H, (float2*)y, w, C, K, cus, stream);
-}
+struct Bank {
+    using Sizes = FirSizes<8192, 16384>;
+    template <int N>
+    static int launch(const void* x, const smfft::FirWindow& w, int C, const void* H, int K, void* y, hipStream_t stream) {
+        const int cus = compute_units();
+        if (cus <= 0) return (int)hipErrorNoDevice;
+        return smfft::large::launch_fir<N>((const float2*)x, (const float2*)H, (float2*)y, w, C, K, cus, stream);
+    }
+    template <int N>
+    static int launch_prepare(const void* taps, int M, int K, int correlate, void* spectra, hipStream_t stream) {
+        const int cus = compute_units();
+        if (cus <= 0) return (int)hipErrorNoDevice;
+        return smfft::large::launch_fir_prepare<N>((const float2*)taps, M, K, correlate, (float2*)spectra, cus, stream);
+    }
+};
+using Api = FirApi<Bank>;
 }  // namespace
 
 extern "C" {
 
 int smfft_large_fir_prepare(const void* d_taps, int n_taps, int n_filters, int FFT_size, int correlate, void* d_spectra, void* hip_stream) {
-    if (!supported(FFT_size) || n_taps < 1 || n_taps >= FFT_size || n_filters <= 0) return -1;
-    const int cus = compute_units();
-    if (cus <= 0) return (int)hipErrorNoDevice;
-    const int c = correlate != 0;
-    if (FFT_size == 8192) return smfft::large::launch_fir_prepare<8192>((const float2*)d_taps, n_taps, n_filters, c, (float2*)d_spectra, cus, (hipStream_t)hip_stream);
-    return smfft::large::launch_fir_prepare<16384>((const float2*)d_taps, n_taps, n_filters, c, (float2*)d_spectra, cus, (hipStream_t)hip_stream);
+    return Api::prepare(d_taps, n_taps, n_filters, FFT_size, correlate, d_spectra, hip_stream);
 }
 
 int smfft_large_fir_launch(const void* d_signal, long long signal_length, int n_channels, const void* d_spectra, int n_filters, int n_taps,
                            int FFT_size, int correlate, void* d_output, void* hip_stream) {
-    const int chk = check(signal_length, n_channels, n_filters, n_taps, FFT_size);
-    if (chk != 0) return chk < 0 ? -1 : 0;
-    return dispatch(d_signal, signal_length, n_channels, d_spectra, n_filters, n_taps, FFT_size, correlate, d_output, (hipStream_t)hip_stream);
+    return Api::launch(d_signal, signal_length, n_channels, d_spectra, n_filters, n_taps, FFT_size, correlate, d_output, hip_stream);
 }
 
 int smfft_large_fir_benchmark(const void* d_signal, long long signal_length, int n_channels, const void* d_spectra, int n_filters, int n_taps,
                               int FFT_size, int correlate, void* d_output, double* FFT_time) {
-    const int chk = check(signal_length, n_channels, n_filters, n_taps, FFT_size);
-    if (chk != 0) return chk < 0 ? -1 : 0;
-    return timed_launch(FFT_time, [&] { return dispatch(d_signal, signal_length, n_channels, d_spectra, n_filters, n_taps, FFT_size, correlate, d_output, nullptr); });
+    return Api::benchmark(d_signal, signal_length, n_channels, d_spectra, n_filters, n_taps, FFT_size, correlate, d_output, FFT_time);
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 """What the CPU tests of the add-on libraries share (test_large_cpu.py, test_large_real_cpu.py, test_large_fir_cpu.py, test_pfb_cpu.py,
-test_pfb_real_cpu.py):
+test_pfb_real_cpu.py, test_fir_real_cpu.py; the FIR checks at the end serve test_fir_cpu.py, the main library's bank, too):
 the per-length flags of the Makefile, the compile of a per-length object to gfx950 assembly as the Makefile compiles it, the fields of
 a kernel descriptor, the declarations of a C header as ctypes signatures, and the walk through a kernel inventory."""
 import ctypes
@@ -207,3 +207,67 @@ def check_pfb_rejections(mirror, stem, samples, bad_lengths):
         assert frames(1 << 20, 1024, p) == -1 and default_tile_run(1024, p) == -1
     for L, _, N, P in bad_lengths:
         assert frames(L, N, P) == -1, (L, N, P)
+
+
+# ------------------------------------------------------------------------------------------------ the three FIR filter banks
+# What test_fir_cpu.py, test_fir_real_cpu.py and test_large_fir_cpu.py hold their banks to.  A bank is named by the prefix of its C
+# functions ("smfft_fir_real") and the lengths it serves.
+def fir_taps_cases(n):
+    return sorted({1, 2, 17, n // 4 + 1, n // 2, n - 1})
+
+
+def fir_length_cases(n, m):
+    """L < M, L < V, L = V, L = k V and L = k V +- 1; a pair and a lone segment, a second segment three outputs short, and
+    (2F + 1) V - 3: more than one workgroup tile of pairs with a ragged last segment"""
+    v, f = n - m + 1, max(1, 4096 // n)
+    return sorted({1, max(1, m // 2), max(1, v // 3), v, v + 1, 2 * v, 2 * v + 1, 3 * v - 1, 3 * v, 3 * v + 1, (2 * f + 1) * v - 3}
+                  | ({2 * v - 3} if v > 2 else set()))
+
+
+def fir_names(prefix):
+    return tuple(f"{prefix}_{f}" for f in ("prepare", "launch", "benchmark"))
+
+
+def check_fir_rejections(lib_path, prefix, sizes):
+    """-1 (or 0 for an empty signal) before any HIP call: run in a process where no GPU is visible, with null pointers.  Every length
+    next to the bank's, every tap count outside 1 ... N - 1, and counts and lengths that are not positive"""
+    import sys
+    code = r"""
+import ctypes, sys
+lib, prefix, sizes = ctypes.CDLL(sys.argv[1]), sys.argv[2], [int(a) for a in sys.argv[3:]]
+prepare, launch, benchmark = (getattr(lib, prefix + "_" + f) for f in ("prepare", "launch", "benchmark"))
+ll = ctypes.c_longlong
+t = ctypes.c_double(0.0)
+lo, hi = sizes[0], sizes[-1]
+off = [lo // 2, 2 * hi, lo - 1, 1000, 0, -lo]
+bad = [(1000, 1, 1, 17, n) for n in off]                                                   # (L, C, K, M, N)
+bad += [(1000, 1, 1, m, n) for n in sizes for m in (0, n, -3)]
+bad += [(1000, 1, k, 17, n) for n in (lo, hi) for k in (0, -2)] + [(1000, c, 1, 17, n) for n in (lo, hi) for c in (0, -1)]
+bad += [(L, 1, 1, 17, n) for n in (lo, hi) for L in (-1, -5)]
+rc = []
+for L, C, K, M, N in bad:
+    for corr in (0, 1):
+        rc.append(launch(None, ll(L), C, None, K, M, N, corr, None, None))
+        rc.append(benchmark(None, ll(L), C, None, K, M, N, corr, None, ctypes.byref(t)))
+for M, K, N in [(17, 1, n) for n in off] + [(m, 1, n) for n in sizes for m in (0, n)] + [(17, k, n) for n in (lo, hi) for k in (0, -1)]:
+    rc.append(prepare(None, M, K, N, 0, None, None))
+empty = [launch(None, ll(0), 1, None, 1, 17, n, 0, None, None) for n in sizes]
+empty += [benchmark(None, ll(0), 1, None, 1, 17, n, 1, None, ctypes.byref(t)) for n in sizes]
+print(rc, empty, t.value)
+sys.exit(0 if rc == [-1] * len(rc) and empty == [0] * (2 * len(sizes)) and t.value == 0.0 else 1)
+"""
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES="-1")
+    p = subprocess.run([sys.executable, "-c", code, lib_path, prefix] + [str(n) for n in sizes], capture_output=True, text=True, timeout=120, env=env)
+    assert p.returncode == 0, p.stdout + p.stderr
+
+
+def check_fir_wrappers_refuse(prepare, launch, sizes):
+    """the mirror's prepare and launch turn the library's -1 into a RuntimeError and refuse an unknown mode themselves, before a device"""
+    import pytest
+    for n in (sizes[0], sizes[-1]):
+        with pytest.raises(RuntimeError):
+            launch(None, 1000, 1, None, 1, n, n, None)
+        with pytest.raises(RuntimeError):
+            prepare(None, None, 0, 1, n)
+        with pytest.raises(ValueError):
+            launch(None, 1000, 1, None, 1, 17, n, None, mode="xcorr")

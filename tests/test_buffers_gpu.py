@@ -24,11 +24,12 @@ import pytest
 from oracle import np_reference as ref
 from tests.fir_gpu_harness import _check_rows
 from tests.fir_gpu_harness import _reference as _fir_reference
+from tests.guarded_region import GUARD      # (128 KiB on each side of every payload, poisoned with a quiet NaN)
+from tests.guarded_region import Region as _Region      # (offsets in whole float2: its default alignment)
+from tests.guarded_region import poison as _poison
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 128 * 1024             # bytes of guard on each side of every payload
-POISON = 0x7FE5A5A5            # quiet NaN with a recognisable payload: guards and the bytes a call must leave alone
 UNWRITTEN = 0xFF               # NaN prefill of the bytes a call must write
 OFFSET = 8                     # payload placement past the guard: an odd float2 index
 MORE_OFFSETS = (0, 4096 - 8)   # and, for the largest batch of every case, these
@@ -46,27 +47,6 @@ def sm():
 
 
 # ------------------------------------------------------------------------------------------------------------- the guarded call
-def _poison(nbytes):
-    return np.full(-(-nbytes // 4), POISON, np.uint32).view(np.uint8)[:nbytes]
-
-
-class _Region:
-    """One device allocation [guard | offset | payload | guard]; `ptr` is the payload's address, `image` the bytes written to the whole
-    allocation (with smfft_memcpy_h2d)."""
-
-    def __init__(self, sm, payload, offset):
-        assert offset >= 0 and offset % 8 == 0
-        self.lo = GUARD + offset
-        self.image = _poison(self.lo + len(payload) + GUARD)
-        self.image[self.lo:self.lo + len(payload)] = payload
-        self.buf = sm.DeviceBuffer(len(self.image))
-        assert sm.lib.smfft_memcpy_h2d(self.buf.ptr, self.image.ctypes.data, len(self.image)) == 0
-        self.ptr = self.buf.ptr + self.lo
-
-    def read(self):
-        return self.buf.to_host(np.uint8, (len(self.image),))
-
-
 def _first_change(now, before, lo):
     idx = np.flatnonzero(now != before)
     return f"{len(idx)} bytes changed, the first at payload offset {int(idx[0]) - lo}" if len(idx) else ""

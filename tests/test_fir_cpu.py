@@ -3,7 +3,6 @@
 load starts, store windows and output indices, the gfx950 code of the new kernels keeps the library's rules (no scratch, no v_sin/v_cos,
 no packed f32, the 16 signal loads of a segment back to back), and the C ABI declares, exports and validates the new entry points
 without a device.  No GPU code is run (hipcc cross-compiles gfx950)."""
-import ctypes
 import os
 import re
 import subprocess
@@ -16,6 +15,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import fir_plan_model as fm  # noqa: E402
 
+from tests import addon_checks as ac  # noqa: E402
+
 HIPCC = "/opt/rocm/bin/hipcc"
 # the Makefile's HIPFLAGS for smfft_fir.o (less -fPIC / -Wall, which change no device code)
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fno-slp-vectorize", "-I" + os.path.join(ROOT, "include")]
@@ -23,15 +24,7 @@ FIR_SRC = os.path.join(ROOT, "smfft_amd", "csrc", "smfft_fir.hip")
 needs_hipcc = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 
 
-def _taps_cases(n):
-    return sorted({1, 2, 17, n // 4 + 1, n // 2, n - 1})
-
-
-def _length_cases(n, m):
-    """L < M, L < V, L = V, L = k V and L = k V +- 1"""
-    v = n - m + 1
-    out = {max(1, m // 2) if m > 1 else 1, max(1, v // 3), v, 3 * v, 3 * v - 1, 3 * v + 1, 2 * v + 1}
-    return sorted(out)
+_taps_cases, _length_cases = ac.fir_taps_cases, ac.fir_length_cases
 
 
 def _grid():
@@ -179,7 +172,7 @@ DECLS = (
     "int smfft_fir_benchmark(const void* d_signal, long long signal_length, int n_channels, const void* d_spectra, int n_filters, int n_taps,\n"
     "                        int FFT_size, int correlate, void* d_output, double* FFT_time);",
 )
-NAMES = ("smfft_fir_prepare", "smfft_fir_launch", "smfft_fir_benchmark")
+NAMES = ac.fir_names("smfft_fir")
 
 
 def test_fir_symbols_are_declared_and_exported():
@@ -200,29 +193,8 @@ def test_fir_symbols_are_declared_and_exported():
 def test_unsupported_combinations_return_minus_one_without_a_device():
     """all validation happens before any HIP call: these return -1 (or 0 for an empty signal) with no device and null pointers"""
     import smfft_amd
-    lib = smfft_amd.lib
-    t = ctypes.c_double(0.0)
-    bad = [  # (L, C, K, M, N)
-        (1000, 1, 1, 17, 1000), (1000, 1, 1, 17, 128), (1000, 1, 1, 17, 8192), (1000, 1, 1, 17, 0),
-        (1000, 1, 1, 0, 1024), (1000, 1, 1, 1024, 1024), (1000, 1, 1, -3, 1024),
-        (1000, 0, 1, 17, 1024), (1000, -1, 1, 17, 1024), (1000, 1, 0, 17, 1024), (1000, 1, -2, 17, 1024),
-        (-1, 1, 1, 17, 1024),
-    ]
-    for L, C, K, M, N in bad:
-        for corr in (0, 1):
-            assert lib.smfft_fir_launch(None, L, C, None, K, M, N, corr, None, None) == -1, (L, C, K, M, N)
-            assert lib.smfft_fir_benchmark(None, L, C, None, K, M, N, corr, None, ctypes.byref(t)) == -1, (L, C, K, M, N)
-    for M, K, N in ((17, 1, 1000), (17, 1, 128), (0, 1, 1024), (1024, 1, 1024), (17, 0, 1024), (17, -1, 1024)):
-        assert lib.smfft_fir_prepare(None, M, K, N, 0, None, None) == -1, (M, K, N)
-    # an empty signal is not an error: nothing is launched
-    assert lib.smfft_fir_launch(None, 0, 1, None, 1, 17, 1024, 0, None, None) == 0
-    assert t.value == 0.0
-    with pytest.raises(RuntimeError):
-        smfft_amd.fir_launch(None, 1000, 1, None, 1, 1024, 1024, None)
-    with pytest.raises(RuntimeError):
-        smfft_amd.fir_prepare(None, None, 0, 1, 1024)
-    with pytest.raises(ValueError):
-        smfft_amd.fir_launch(None, 1000, 1, None, 1, 17, 1024, None, mode="xcorr")
+    ac.check_fir_rejections(smfft_amd.LIB_PATH, "smfft_fir", (256, 512, 1024, 2048, 4096))
+    ac.check_fir_wrappers_refuse(smfft_amd.fir_prepare, smfft_amd.fir_launch, (256, 4096))
 
 
 def test_default_fft_size_rule():

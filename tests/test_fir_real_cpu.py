@@ -23,7 +23,7 @@ HIPCC = ac.HIPCC
 CSRC = ac.CSRC
 LIB = os.path.join(ROOT, "smfft_amd", "libsmfft_fir_real.so")
 SIZES = (256, 512, 1024, 2048, 4096)
-NAMES = ("smfft_fir_real_prepare", "smfft_fir_real_launch", "smfft_fir_real_benchmark")
+NAMES = ac.fir_names("smfft_fir_real")
 LDS_BYTES = 4096 // 16 * 17 * 8
 needs_hipcc = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 
@@ -36,15 +36,7 @@ def fir_lib():
 
 
 # ---- the model ---------------------------------------------------------------------------------------
-def _taps_cases(n):
-    return (1, 2, 17, n // 4 + 1, n - 1)
-
-
-def _length_cases(n, m):
-    """a row shorter than the taps, one segment, an absent partner, a full pair, a pair plus a lone segment, and (2F + 1) V - 3: more
-    than one workgroup tile of pairs with a ragged last segment"""
-    v, f = n - m + 1, 4096 // n
-    return sorted({1, max(1, m // 2), v, v + 1, 2 * v, 2 * v + 1, (2 * f + 1) * v - 3} - {0, -1, -2})
+_taps_cases, _length_cases = ac.fir_taps_cases, ac.fir_length_cases
 
 
 @pytest.mark.parametrize("n", SIZES)
@@ -266,42 +258,12 @@ def test_library_exports_exactly_the_three_symbols(fir_lib):
 
 def test_unsupported_combinations_return_minus_one_without_a_device(fir_lib):
     """-1 (or 0 for an empty signal) before any HIP call: run in a process where no GPU is visible, with null pointers"""
-    code = r"""
-import ctypes, sys
-lib = ctypes.CDLL(sys.argv[1])
-ll = ctypes.c_longlong
-t = ctypes.c_double(0.0)
-bad = [  # (L, C, K, M, N)
-    (1000, 1, 1, 17, 128), (1000, 1, 1, 17, 8192), (1000, 1, 1, 17, 1000), (1000, 1, 1, 17, 0), (1000, 1, 1, 17, -1024),
-    (1000, 1, 1, 0, 1024), (1000, 1, 1, 1024, 1024), (1000, 1, 1, 4096, 4096), (1000, 1, 1, 256, 256), (1000, 1, 1, -3, 2048),
-    (1000, 1, 0, 17, 1024), (1000, 1, -2, 17, 4096), (1000, 0, 1, 17, 256), (1000, -1, 1, 17, 512),
-    (-1, 1, 1, 17, 1024), (-5, 1, 1, 17, 4096),
-]
-rc = []
-for L, C, K, M, N in bad:
-    for corr in (0, 1):
-        rc.append(lib.smfft_fir_real_launch(None, ll(L), C, None, K, M, N, corr, None, None))
-        rc.append(lib.smfft_fir_real_benchmark(None, ll(L), C, None, K, M, N, corr, None, ctypes.byref(t)))
-for M, K, N in ((17, 1, 128), (17, 1, 8192), (17, 1, 1000), (0, 1, 1024), (1024, 1, 1024), (4096, 1, 4096), (17, 0, 1024), (17, -1, 4096)):
-    rc.append(lib.smfft_fir_real_prepare(None, M, K, N, 0, None, None))
-empty = [lib.smfft_fir_real_launch(None, ll(0), 1, None, 1, 17, n, 0, None, None) for n in (256, 512, 1024, 2048, 4096)]
-empty += [lib.smfft_fir_real_benchmark(None, ll(0), 1, None, 1, 17, n, 1, None, ctypes.byref(t)) for n in (256, 512, 1024, 2048, 4096)]
-print(rc, empty, t.value)
-sys.exit(0 if rc == [-1] * len(rc) and empty == [0] * 10 and t.value == 0.0 else 1)
-"""
-    env = dict(os.environ, HIP_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES="-1")
-    p = subprocess.run([sys.executable, "-c", code, fir_lib], capture_output=True, text=True, timeout=120, env=env)
-    assert p.returncode == 0, p.stdout + p.stderr
+    ac.check_fir_rejections(fir_lib, "smfft_fir_real", SIZES)
 
 
 def test_python_wrappers_refuse_before_a_device(fir_lib):
     from smfft_amd import fir_real
-    with pytest.raises(RuntimeError):
-        fir_real.launch(None, 1000, 1, None, 1, 1024, 1024, None)
-    with pytest.raises(RuntimeError):
-        fir_real.prepare(None, None, 0, 1, 1024)
-    with pytest.raises(ValueError):
-        fir_real.launch(None, 1000, 1, None, 1, 17, 1024, None, mode="xcorr")
+    ac.check_fir_wrappers_refuse(fir_real.prepare, fir_real.launch, SIZES)
     assert fir_real.benchmark(None, 1000, 1, None, 1, 17, 8192, None) == (-1, 0.0)
     # complex input is refused, never stripped of its imaginary part
     for x, h in ((np.zeros(10, np.complex64), np.zeros(17, np.float32)), (np.zeros(10, np.float32), np.zeros(17, np.complex128))):

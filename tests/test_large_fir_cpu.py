@@ -21,7 +21,7 @@ HIPCC = "/opt/rocm/bin/hipcc"
 CSRC = os.path.join(ROOT, "smfft_amd", "csrc")
 LIB = os.path.join(ROOT, "smfft_amd", "libsmfft_large_fir.so")
 SIZES = (8192, 16384)
-NAMES = ("smfft_large_fir_prepare", "smfft_large_fir_launch", "smfft_large_fir_benchmark")
+NAMES = ac.fir_names("smfft_large_fir")
 LDS_BYTES = {8192: 8 * 16 * (8192 // 16 + 2), 16384: 8 * 16 * (16384 // 16 + 2)}      # LargeGeometry<N>::kLdsBytes
 needs_hipcc = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 
@@ -34,13 +34,7 @@ def fir_lib():
 
 
 # ---- the model ---------------------------------------------------------------------------------------
-def _taps_cases(n):
-    return (1, 17, n // 4 + 1, n // 2, n - 1)
-
-
-def _length_cases(n, m):
-    v = n - m + 1
-    return sorted({1, max(1, m // 2), max(1, v // 3), v, v + 1, 2 * v - 3 if v > 2 else 1, 3 * v, 3 * v - 1, 3 * v + 1})
+_taps_cases, _length_cases = ac.fir_taps_cases, ac.fir_length_cases
 
 
 @pytest.mark.parametrize("n", SIZES)
@@ -223,42 +217,12 @@ def test_library_exports_exactly_the_three_symbols(fir_lib):
 
 def test_unsupported_combinations_return_minus_one_without_a_device(fir_lib):
     """-1 (or 0 for an empty signal) before any HIP call: run in a process where no GPU is visible, with null pointers"""
-    code = r"""
-import ctypes, sys
-lib = ctypes.CDLL(sys.argv[1])
-ll = ctypes.c_longlong
-t = ctypes.c_double(0.0)
-bad = [  # (L, C, K, M, N)
-    (1000, 1, 1, 17, 4096), (1000, 1, 1, 17, 32768), (1000, 1, 1, 17, 8191), (1000, 1, 1, 17, 0),
-    (1000, 1, 1, 0, 8192), (1000, 1, 1, 8192, 8192), (1000, 1, 1, 16384, 16384), (1000, 1, 1, -3, 16384),
-    (1000, 1, 0, 17, 8192), (1000, 1, -2, 17, 16384), (1000, 0, 1, 17, 8192), (1000, -1, 1, 17, 16384),
-    (-1, 1, 1, 17, 8192), (-5, 1, 1, 17, 16384),
-]
-rc = []
-for L, C, K, M, N in bad:
-    for corr in (0, 1):
-        rc.append(lib.smfft_large_fir_launch(None, ll(L), C, None, K, M, N, corr, None, None))
-        rc.append(lib.smfft_large_fir_benchmark(None, ll(L), C, None, K, M, N, corr, None, ctypes.byref(t)))
-for M, K, N in ((17, 1, 4096), (17, 1, 32768), (0, 1, 8192), (8192, 1, 8192), (16384, 1, 16384), (17, 0, 8192), (17, -1, 16384)):
-    rc.append(lib.smfft_large_fir_prepare(None, M, K, N, 0, None, None))
-empty = [lib.smfft_large_fir_launch(None, ll(0), 1, None, 1, 17, n, 0, None, None) for n in (8192, 16384)]
-empty += [lib.smfft_large_fir_benchmark(None, ll(0), 1, None, 1, 17, n, 1, None, ctypes.byref(t)) for n in (8192, 16384)]
-print(rc, empty, t.value)
-sys.exit(0 if rc == [-1] * len(rc) and empty == [0] * 4 and t.value == 0.0 else 1)
-"""
-    env = dict(os.environ, HIP_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES="-1")
-    p = subprocess.run([sys.executable, "-c", code, fir_lib], capture_output=True, text=True, timeout=120, env=env)
-    assert p.returncode == 0, p.stdout + p.stderr
+    ac.check_fir_rejections(fir_lib, "smfft_large_fir", SIZES)
 
 
 def test_python_wrappers_refuse_before_a_device(fir_lib):
     from smfft_amd import large_fir
-    with pytest.raises(RuntimeError):
-        large_fir.launch(None, 1000, 1, None, 1, 8192, 8192, None)
-    with pytest.raises(RuntimeError):
-        large_fir.prepare(None, None, 0, 1, 16384)
-    with pytest.raises(ValueError):
-        large_fir.launch(None, 1000, 1, None, 1, 17, 8192, None, mode="xcorr")
+    ac.check_fir_wrappers_refuse(large_fir.prepare, large_fir.launch, SIZES)
 
 
 def test_default_fft_size_rule():

@@ -5,13 +5,11 @@ grid; the prepared spectra; a caller's stream; the benchmark form; 64-bit output
 they did.
 
 Tolerances per (channel, filter) row: those of tests/test_fir_gpu.py (relL2 <= 1e-6, max <= 5e-6, with its denominators)."""
-import ctypes
-
 import numpy as np
 import pytest
 
 from oracle.np_reference import MAX_ABS_TOL, REL_L2_TOL
-from tests.fir_gpu_harness import GUARD, MODES, _check_rows, _rand, _reference, _sampled_windows
+from tests.fir_gpu_harness import GUARD, MODES, Bank, _check_rows, _rand, _reference
 
 import large_fir_model as lfm  # noqa: E402  (tools/ is on the path once tests.fir_gpu_harness is imported)
 
@@ -35,35 +33,14 @@ def lf():
     return large_fir
 
 
-def _run(sm, lf, x, h, N, mode, spectra=None):
-    """prepare + launch through the device-pointer API into a NaN-prefilled output followed by a guard region; returns the (C, K, L)
-    result after checking that the guard is untouched and no NaN of the prefill is left"""
-    C, L = x.shape
-    K, M = h.shape
-    dx, dh = sm.DeviceBuffer.from_host(x), sm.DeviceBuffer.from_host(h)
-    if spectra is None:
-        dspec = sm.DeviceBuffer(K * N * 8)
-        lf.prepare(dh.ptr, dspec.ptr, M, K, N, mode)
-    else:
-        dspec = sm.DeviceBuffer.from_host(spectra)
-    total = C * K * L
-    dout = sm.DeviceBuffer((total + GUARD) * 8)
-    assert sm.lib.smfft_memset(dout.ptr, 0xFF, total * 8) == 0
-    assert sm.lib.smfft_memset(dout.ptr + total * 8, 0x5A, GUARD * 8) == 0
-    lf.launch(dx.ptr, L, C, dspec.ptr, K, M, N, dout.ptr, mode)
-    assert sm.lib.smfft_synchronize() == 0
-    raw = dout.to_host(np.uint8, ((total + GUARD) * 8,))
-    assert np.all(raw[total * 8:] == 0x5A), "the kernel wrote past its output"
-    out = raw[:total * 8].view(np.complex64).reshape(C, K, L)
-    assert np.all(np.isfinite(out.view(np.float32))), "outputs left unwritten"
-    for b in (dx, dh, dspec, dout):
-        b.free()
-    return out
+@pytest.fixture(scope="module")
+def bank(sm, lf):
+    return Bank.large(sm, lf)
 
 
 @pytest.mark.parametrize("N", SIZES)
 @pytest.mark.parametrize("mode", MODES)
-def test_filter_bank_matches_numpy(sm, lf, N, mode):
+def test_filter_bank_matches_numpy(sm, lf, bank, N, mode):
     rng = np.random.default_rng(N + (mode == "correlate"))
     for M in (1, 17, N // 4 + 1, N - 1):
         V = N - M + 1
@@ -72,7 +49,7 @@ def test_filter_bank_matches_numpy(sm, lf, N, mode):
         for L in lengths:
             for C, K in ((1, 1), (3, 5), (1, 64), (3, 64)):
                 x, h = _rand(rng, (C, L)), _rand(rng, (K, M))
-                got = _run(sm, lf, x, h, N, mode)
+                got = bank.run(x, h, N, mode)
                 _check_rows(got, _reference(x, h, mode == "correlate"), f"N={N} {mode} M={M} L={L} C={C} K={K}", x, h)
 
 
@@ -92,58 +69,18 @@ def test_host_convenience(sm, lf):
 
 
 @pytest.mark.parametrize("N,M", [(8192, 2049), (16384, 4097)])
-def test_k_filters_equal_k_single_launches(sm, lf, N, M):
+def test_k_filters_equal_k_single_launches(bank, N, M):
     """K = 200 on a short signal (three segments): every row equals the K = 1 launch of its filter to the bit.  At 8192 the K = 200
     launch runs the held form -- on 256 CUs 67 filter groups of 3, the last of 2 (fir_filter_group_size(3, 200, CUs)) -- and the
     single-filter launches the recompute form."""
-    rng = np.random.default_rng(N)
-    V, K = N - M + 1, 200
-    L = 3 * V - 7
-    x, h = _rand(rng, (1, L)), _rand(rng, (K, M))
-    for mode in MODES:
-        dx, dh = sm.DeviceBuffer.from_host(x), sm.DeviceBuffer.from_host(h)
-        dspec, dout, d1 = sm.DeviceBuffer(K * N * 8), sm.DeviceBuffer(K * L * 8), sm.DeviceBuffer(L * 8)
-        lf.prepare(dh.ptr, dspec.ptr, M, K, N, mode)
-        lf.launch(dx.ptr, L, 1, dspec.ptr, K, M, N, dout.ptr, mode)
-        assert sm.lib.smfft_synchronize() == 0
-        all_rows = dout.to_host(np.complex64, (K, L))
-        for k in range(K):
-            lf.launch(dx.ptr, L, 1, dspec.ptr + k * N * 8, 1, M, N, d1.ptr, mode)
-            assert sm.lib.smfft_synchronize() == 0
-            one = d1.to_host(np.complex64, (L,))
-            assert np.array_equal(one.view(np.uint32), all_rows[k].view(np.uint32)), (mode, k)
-        _check_rows(all_rows[None, ::37], _reference(x, h[::37], mode == "correlate"), f"K=200 N={N} {mode}", x, h[::37])
-        for b in (dx, dh, dspec, dout, d1):
-            b.free()
+    bank.check_group_split(N, M, 3 * (N - M + 1) - 7)
 
 
 @pytest.mark.parametrize("N", SIZES)
-def test_prepared_spectra(sm, lf, N):
+def test_prepared_spectra(bank, N):
     """smfft_large_fir_prepare = fft(pad(g)) / N within the per-FFT tolerances; a launch with NumPy-prepared spectra gives the library's
     result"""
-    rng = np.random.default_rng(3 * N)
-    K = 7
-    for mode in MODES:
-        for M in (1, 17, N // 4 + 1, N - 1):
-            h = _rand(rng, (K, M))
-            dh, dspec = sm.DeviceBuffer.from_host(h), sm.DeviceBuffer(K * N * 8)
-            lf.prepare(dh.ptr, dspec.ptr, M, K, N, mode)
-            assert sm.lib.smfft_synchronize() == 0
-            got = dspec.to_host(np.complex64, (K, N))
-            want = lfm.spectra(h, N, mode == "correlate")
-            for k in range(K):
-                d = got[k] - want[k]
-                l2 = np.linalg.norm(d) / np.linalg.norm(want[k])
-                mx = np.max(np.abs(d)) / np.max(np.abs(want[k]))
-                assert l2 <= REL_L2_TOL and mx <= MAX_ABS_TOL, (mode, M, k, l2, mx)
-            dh.free()
-            dspec.free()
-            x = _rand(rng, (2, 3 * (N - M + 1) + 5))
-            lib_out = _run(sm, lf, x, h, N, mode)
-            np_out = _run(sm, lf, x, h, N, mode, spectra=want.astype(np.complex64))
-            want_y = _reference(x, h, mode == "correlate")
-            _check_rows(np_out, want_y, f"NumPy spectra N={N} {mode} M={M}", x, h)
-            _check_rows(lib_out, np_out.astype(np.complex128), f"library vs NumPy spectra N={N} {mode} M={M}", x, h)
+    bank.check_prepared_spectra(N)
 
 
 def test_prepare_more_filters_than_the_grid(sm, lf):
@@ -164,51 +101,19 @@ def test_prepare_more_filters_than_the_grid(sm, lf):
     dspec.free()
 
 
-def test_caller_stream(sm, lf):
+def test_caller_stream(bank):
     """prepare and launch on a stream from hipStreamCreate, then hipStreamSynchronize"""
-    hip = ctypes.CDLL("libamdhip64.so")
-    hip.hipStreamCreate.argtypes = [ctypes.POINTER(ctypes.c_void_p)]
-    hip.hipStreamSynchronize.argtypes = [ctypes.c_void_p]
-    hip.hipStreamDestroy.argtypes = [ctypes.c_void_p]
-    stream = ctypes.c_void_p()
-    assert hip.hipStreamCreate(ctypes.byref(stream)) == 0 and stream.value
-    rng = np.random.default_rng(11)
-    for N, M in ((8192, 2049), (16384, 4097)):
-        C, K, L = 2, 9, 100000
-        x, h = _rand(rng, (C, L)), _rand(rng, (K, M))
-        for mode in MODES:
-            dx, dh = sm.DeviceBuffer.from_host(x), sm.DeviceBuffer.from_host(h)
-            dspec, dout = sm.DeviceBuffer(K * N * 8), sm.DeviceBuffer(C * K * L * 8)
-            assert sm.lib.smfft_memset(dout.ptr, 0xFF, dout.nbytes) == 0
-            assert sm.lib.smfft_synchronize() == 0
-            lf.prepare(dh.ptr, dspec.ptr, M, K, N, mode, stream=stream.value)
-            lf.launch(dx.ptr, L, C, dspec.ptr, K, M, N, dout.ptr, mode, stream=stream.value)
-            assert hip.hipStreamSynchronize(stream) == 0
-            _check_rows(dout.to_host(np.complex64, (C, K, L)), _reference(x, h, mode == "correlate"), f"stream N={N} {mode}", x, h)
-            for b in (dx, dh, dspec, dout):
-                b.free()
-    assert hip.hipStreamDestroy(stream) == 0
+    bank.check_caller_stream([(8192, 2049), (16384, 4097)], C=2, K=9, L=100000)
 
 
 @pytest.mark.parametrize("N", SIZES)
-def test_benchmark_form(sm, lf, N):
-    rng = np.random.default_rng(12)
-    M, K, L = 1000, 3, 60000
-    x, h = _rand(rng, (1, L)), _rand(rng, (K, M))
-    dx, dh = sm.DeviceBuffer.from_host(x), sm.DeviceBuffer.from_host(h)
-    dspec, dout = sm.DeviceBuffer(K * N * 8), sm.DeviceBuffer(K * L * 8)
-    lf.prepare(dh.ptr, dspec.ptr, M, K, N)
-    t = ctypes.c_double(1.0)
-    assert lf.lib().smfft_large_fir_benchmark(dx.ptr, L, 1, dspec.ptr, K, M, N, 0, dout.ptr, ctypes.byref(t)) == 0
-    assert t.value > 1.0
-    _check_rows(dout.to_host(np.complex64, (1, K, L)), _reference(x, h, False), "benchmark form", x, h)
-    for b in (dx, dh, dspec, dout):
-        b.free()
+def test_benchmark_form(bank, N):
+    bank.check_benchmark_form(N, M=1000, K=3, L=60000)
 
 
 @pytest.mark.parametrize("N", SIZES)
 @pytest.mark.parametrize("mode", MODES)
-def test_persistent_loop_several_times_round_the_grid(sm, lf, N, mode):
+def test_persistent_loop_several_times_round_the_grid(sm, lf, bank, N, mode):
     """M = N - 1 (V = 2 outputs per segment), C = 3, K = 3, S = 301 segments per channel: 2709 units, more than five times the grid
     of 8192 and ten times that of 16384; L = 2 S - 1 leaves the last segment one output.  Every row against fp64."""
     M, C, K, S = N - 1, 3, 3, 301
@@ -217,13 +122,13 @@ def test_persistent_loop_several_times_round_the_grid(sm, lf, N, mode):
     assert 0 < 5 * grid <= C * S * K and lfm.Window(L, N, M, False).segments() == S
     rng = np.random.default_rng(12288 + N + (mode == "correlate"))
     x, h = _rand(rng, (C, L)), _rand(rng, (K, M))
-    got = _run(sm, lf, x, h, N, mode)
+    got = bank.run(x, h, N, mode)
     _check_rows(got, _reference(x, h, mode == "correlate"), f"persistent loop N={N} {mode}", x, h)
 
 
 @pytest.mark.parametrize("N,M", [(8192, 2049), (16384, 4097)])
 @pytest.mark.parametrize("mode", MODES)
-def test_persistent_loop_at_a_realistic_shape(sm, lf, N, M, mode):
+def test_persistent_loop_at_a_realistic_shape(sm, lf, bank, N, M, mode):
     """C = 3 channels of L = 16e6 samples, K = 2: thousands of units on a grid of a few hundred.  Sampled windows against np.convolve /
     np.correlate: the first and last of every (channel, filter) row, one in the middle, and the one of the first unit of the grid's
     second round."""
@@ -250,46 +155,21 @@ def test_persistent_loop_at_a_realistic_shape(sm, lf, N, M, mode):
         guard = np.empty(GUARD * 8, np.uint8)
         assert sm.lib.smfft_memcpy_d2h(guard.ctypes.data, dout.ptr + C * K * L * 8, GUARD * 8) == 0
         assert np.all(guard == 0x5A), "the kernel wrote past its output"
-        _sampled_windows(sm, dout, x, h, L, starts, mode, f"L=16e6 N={N} {mode}", W)
+        bank.sampled_windows(dout, x, h, L, starts, mode, f"L=16e6 N={N} {mode}", W)
     finally:
         for b in (dx, dh, dspec, dout):
             b.free()
 
 
 @pytest.mark.parametrize("N,M", [(8192, 2049), (16384, 4097)])
-def test_output_offsets_beyond_two_to_the_31(sm, lf, N, M):
+def test_output_offsets_beyond_two_to_the_31(bank, N, M):
     """C = 1, K = 64, L = 2^25 + 1000: 2.15e9 output elements (16 GiB); sampled windows of the last filter rows against np.convolve /
     np.correlate on the matching input slice"""
     K, L = 64, (1 << 25) + 1000
     rng = np.random.default_rng(5)
     x = rng.standard_normal((1, 2 * L), dtype=np.float32).view(np.complex64)
     h = _rand(rng, (K, M))
-    dx, dh = sm.DeviceBuffer.from_host(x), sm.DeviceBuffer.from_host(h)
-    dspec, dout = sm.DeviceBuffer(K * N * 8), sm.DeviceBuffer(K * L * 8)
-    W = 3000
-    # row K - 1 crosses element 2^31 (byte offset 16 GiB) at n = 2^31 - (K - 1) L: one window straddles it, the last ones lie beyond it
-    cross = (1 << 31) - (K - 1) * L
-    starts = [0, L // 2 + 17, cross - 700, L - 5 * N, L - W]
-    assert all(0 <= n0 and n0 + W <= L for n0 in starts) and (K - 1) * L + L - W >= 1 << 31
-    try:
-        for mode in MODES:
-            lf.prepare(dh.ptr, dspec.ptr, M, K, N, mode)
-            lf.launch(dx.ptr, L, 1, dspec.ptr, K, M, N, dout.ptr, mode)
-            assert sm.lib.smfft_synchronize() == 0
-            for k in (K - 2, K - 1):
-                hk = h[k:k + 1]
-                dk = _Row(dout.ptr + k * L * 8)
-                _sampled_windows(sm, dk, x, hk, L, [starts], mode, f"2^31 N={N} {mode} k={k}", W)
-    finally:
-        for b in (dx, dh, dspec, dout):
-            b.free()
-
-
-class _Row:
-    """a (channel, filter) row of a device output, as the `dout` of _sampled_windows with C = K = 1"""
-
-    def __init__(self, ptr):
-        self.ptr = ptr
+    bank.check_output_offsets(x, h, N)
 
 
 def test_neighbours_keep_their_limits(sm, lf):

@@ -1,5 +1,5 @@
 """tests/pfb_gpu_harness.py without a device: the guarded run and the row checks that hold the filter bank kernels to their buffer contract
-and their bounds are held to what they claim.  smfft_amd is stood in for by numpy memory (HOST: DeviceBuffer, smfft_memset,
+and their bounds are held to what they claim.  smfft_amd is stood in for by numpy memory (tests/host_device.py: DeviceBuffer, smfft_memset,
 smfft_synchronize), a launch by a Python function that reads and writes through the pointers it is given.
 
 The guarded run, in the complex, the real and the integrated-spectra (T = 2) layout at N = 256, P = 2, C = 2, F = 3 with a ragged tail:
@@ -9,48 +9,16 @@ each fail, with the message that names the fault.
 The row checks, at (N, P) = (256, 4): the model's rows plus a perturbation of a quarter of the bound, rounded to fp32, pass; the same at
 twice the bound fails (rounding the reference to fp32 costs at most 6e-8 of these scales).  The real bank's Nyquist component alone,
 moved by twice the row's max bound, fails, and the message carries the element-0 figure."""
-import ctypes
 import re
-import types
 
 import numpy as np
 import pytest
 
 from tests import pfb_gpu_harness as gh
+from tests.host_device import HOST
+from tests.host_device import at as _at
 
 N, P, C, F, T = 256, 2, 2, 3, 2
-
-
-# ---- numpy memory in the place of the device ------------------------------------------------------------------------------------------
-class HostBuffer:
-    def __init__(self, nbytes):
-        self.mem, self.nbytes = np.zeros(nbytes, np.uint8), nbytes
-        self.ptr = self.mem.ctypes.data
-
-    @classmethod
-    def from_host(cls, a):
-        b = cls(a.nbytes)
-        b.mem[:] = np.ascontiguousarray(a).reshape(-1).view(np.uint8)
-        return b
-
-    def to_host(self, dtype, shape):
-        return self.mem.view(dtype).reshape(shape).copy()
-
-    def free(self):
-        self.mem = None
-
-
-def _memset(ptr, byte, nbytes):
-    ctypes.memset(ptr, byte, nbytes)
-    return 0
-
-
-HOST = types.SimpleNamespace(DeviceBuffer=HostBuffer, lib=types.SimpleNamespace(smfft_memset=_memset, smfft_synchronize=lambda: 0))
-
-
-def _at(ptr, dtype, n):
-    """n elements of dtype at the address ptr; negative indices are not meant: pass ptr - k * itemsize"""
-    return np.ctypeslib.as_array(ctypes.cast(ptr, ctypes.POINTER(ctypes.c_uint8)), (n * np.dtype(dtype).itemsize,)).view(dtype)
 
 
 # ---- the three layouts ------------------------------------------------------------------------------------------------------------------

@@ -46,6 +46,7 @@ import pytest
 
 from oracle import np_reference as ref
 from tests import probe_cases as pc
+from tests.fir_gpu_harness import GRID_CAP
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
 import fir_plan_model as fm  # noqa: E402
@@ -374,7 +375,6 @@ def assert_isolated_and_exact(clean, dirty, e, kinds, real_in, real_out, what):
 
 
 # ---------------------------------------------------------------------------------------------------- B: the FIR filter banks
-GRID_CAP = 12288               # smfft_fir.hip kFirGridCap
 FIR_MODES = ("convolve", "correlate")
 
 

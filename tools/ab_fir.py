@@ -19,23 +19,12 @@ import torch
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
 import smfft_amd as sm  # noqa: E402
+from ab_fir_common import as_tensor, round_robin  # noqa: E402  (beside this file)
 
 FP32_PEAK_TFLOPS = 157.3     # bench.py
 HBM_TBS = 8.0
-TARGET_WORKGROUPS = 2048     # smfft_fir.hip, kFirTargetWorkgroups
+TARGET_WORKGROUPS = 2048     # smfft_fir_kernel.hpp, kFirTargetWorkgroups
 REPS = int(sys.argv[1]) if len(sys.argv) > 1 else 9
-
-
-class _Raw:
-    """a device pointer as a torch tensor (no copy)"""
-
-    def __init__(self, ptr, shape, typestr):
-        self.__cuda_array_interface__ = {"shape": shape, "typestr": typestr, "data": (ptr, False), "version": 3}
-
-
-def as_tensor(ptr, shape, dtype=torch.complex64):
-    typestr = {torch.complex64: "<c8", torch.float32: "<f4"}[dtype]
-    return torch.as_tensor(_Raw(ptr, tuple(shape), typestr), device="cuda")
 
 
 def groups_of(tiles, K):
@@ -47,26 +36,6 @@ def transforms(C, L, K, N, M):
     S = -(-L // (N - M + 1))
     tiles = -(-(C * S) // (4096 // N))
     return C * S * (groups_of(tiles, K) + K)
-
-
-def timed(fn, stream):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record(stream)
-    fn()
-    b.record(stream)
-    b.synchronize()
-    return a.elapsed_time(b)
-
-
-def round_robin(fns, stream):
-    ts = {n: [] for n in fns}
-    for name, fn in fns.items():
-        fn(), fn()
-    torch.cuda.synchronize()
-    for _ in range(REPS):
-        for name, fn in fns.items():
-            ts[name].append(timed(fn, stream))
-    return {n: sorted(v) for n, v in ts.items()}
 
 
 def report(name, v, C, L, K, N, M):
@@ -138,7 +107,7 @@ def main():
     print(f"max |fused - unfused| / max |unfused| = {d:.2e};  fused vs np.convolve (last row, last {W}): "
           f"relL2 {np.linalg.norm(got - want) / np.linalg.norm(want):.2e}", flush=True)
     print(f"main configuration: C={C} L=2^24 K={K} M={M} N={N} (V={V}, S={S}), output {out_bytes / 2**30:.0f} GiB, {REPS} reps round robin", flush=True)
-    ts = round_robin(fns, stream)
+    ts = round_robin(fns, REPS, stream)
     med = {name: report(name, v, C, L, K, N, M) for name, v in ts.items()}
     for where in ("smfft_malloc_written_for output", "hipMalloc output"):
         print(f"  speed-up fused over unfused, {where}: {med[f'unfused ({where})'] / med[f'fused   ({where})']:.2f} x", flush=True)
@@ -157,7 +126,7 @@ def main():
             out = torch.empty((C, K, L), dtype=torch.complex64, device="cuda")
             fn = (lambda H=H, K=K, M=M, N=N, out=out:
                   sm.fir_launch(x.data_ptr(), L, C, H.data_ptr(), K, M, N, out.data_ptr(), "convolve", stream=sp))
-            v = round_robin({"f": fn}, stream)["f"]
+            v = round_robin({"f": fn}, REPS, stream)["f"]
             report(f"N={N:4d} M={M:4d} K={K:3d}", v, C, L, K, N, M)
             del out, H, h
             torch.cuda.empty_cache()

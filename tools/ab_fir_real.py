@@ -23,31 +23,10 @@ ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
 import smfft_amd as sm  # noqa: E402
 from smfft_amd import fir_real  # noqa: E402
+from ab_fir_common import round_robin  # noqa: E402  (beside this file)
+from ab_fir_common import timed as events  # noqa: E402
 
 COPY = "copy of the real bank's bytes"
-
-
-def events(fn, stream):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record(stream)
-    fn()
-    b.record(stream)
-    b.synchronize()
-    return a.elapsed_time(b)
-
-
-def round_robin(fns, reps):
-    """{name: the sorted times of `reps` calls}; every fn returns its own milliseconds and is warmed up twice first"""
-    ts = {n: [] for n in fns}
-    for fn in fns.values():
-        fn(), fn()
-    torch.cuda.synchronize()
-    for rep in range(reps):
-        # forwards and backwards in turn: what ran just before an entry (and left its bytes in the caches) changes with the direction,
-        # so two builds of the same kernel are not timed in one fixed order
-        for name, fn in (list(fns.items()) if rep % 2 == 0 else reversed(list(fns.items()))):
-            ts[name].append(fn())
-    return {n: sorted(v) for n, v in ts.items()}
 
 
 def main():
@@ -134,7 +113,7 @@ def main():
         fns["complex bank on the cast signal"] = cplx
         fns["cast + complex bank"] = cast_and_cplx
         fns[COPY] = lambda: events(lambda: dst.copy_(src), stream)
-        ts = round_robin(fns, args.reps)
+        ts = round_robin(fns, args.reps, alternate=True)      # every fn returns its own milliseconds
         q = {n: (v[len(v) // 4], v[len(v) // 2], v[(3 * len(v)) // 4]) for n, v in ts.items()}
         for n, v in ts.items():
             lo, med, hi = q[n]

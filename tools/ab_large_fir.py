@@ -28,37 +28,11 @@ import numpy as np
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 sys.path.insert(0, ROOT)
+from ab_fir_common import as_tensor, round_robin  # noqa: E402  (beside this file; imports torch on first use)
 
 FP32_PEAK_TFLOPS = 157.3     # bench.py
 HBM_TBS = 8.0
 MAIN = ((8192, 2049), (16384, 4097))
-
-
-class _Raw:
-    """a device pointer as a torch tensor (no copy)"""
-
-    def __init__(self, ptr, shape):
-        self.__cuda_array_interface__ = {"shape": shape, "typestr": "<c8", "data": (ptr, False), "version": 3}
-
-
-def timed(torch, fn, stream):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record(stream)
-    fn()
-    b.record(stream)
-    b.synchronize()
-    return a.elapsed_time(b)
-
-
-def round_robin(torch, fns, stream, reps):
-    ts = {n: [] for n in fns}
-    for fn in fns.values():
-        fn(), fn()
-    torch.cuda.synchronize()
-    for _ in range(reps):
-        for name, fn in fns.items():
-            ts[name].append(timed(torch, fn, stream))
-    return {n: sorted(v) for n, v in ts.items()}
 
 
 def report(name, v, C, L, K, N, transforms):
@@ -89,7 +63,7 @@ def main_config(torch, sm, large, lf, N, M, args, rng):
     out_bytes = C * K * L * 8
     pw = ctypes.c_void_p()
     assert sm.lib.smfft_malloc_written_for(ys.data_ptr(), out_bytes, ctypes.byref(pw)) == 0
-    placed = torch.as_tensor(_Raw(pw.value, (C, K, L)), device="cuda")
+    placed = as_tensor(pw.value, (C, K, L))
     xpad = torch.zeros((C, (S - 1) * V + N), dtype=torch.complex64, device="cuda")
     xpad[:, M - 1:M - 1 + L] = x
 
@@ -158,7 +132,7 @@ def main_config(torch, sm, large, lf, N, M, args, rng):
         print(f"N={N}: recompute form (A/B build) bit-identical to the shipped held form: "
               f"{bool(torch.equal(torch.view_as_real(plain), torch.view_as_real(placed)))}", flush=True)
     print(f"main configuration: C={C} L=2^24 K={K} M={M} N={N} (V={V}, S={S}), output {out_bytes / 2**30:.0f} GiB, {args.reps} reps round robin", flush=True)
-    ts = round_robin(torch, fns, stream, args.reps)
+    ts = round_robin(fns, args.reps, stream)
     med = {}
     for name, v in ts.items():
         n = 4096 if name.startswith("old path") else N
@@ -183,7 +157,7 @@ def sweep(torch, lf, x, N, M, args, rng):
         lf.prepare(h.data_ptr(), H.data_ptr(), M, K, N, "convolve", stream=sp)
         out = torch.empty((C, K, L), dtype=torch.complex64, device="cuda")
         fn = (lambda H=H, K=K, out=out: lf.launch(x.data_ptr(), L, C, H.data_ptr(), K, M, N, out.data_ptr(), "convolve", stream=sp))
-        v = round_robin(torch, {"f": fn}, stream, args.reps)["f"]
+        v = round_robin({"f": fn}, args.reps, stream)["f"]
         report(f"N={N:5d} M={M:4d} K={K:3d}", v, C, L, K, N, C * S * (1 + K) if N == 8192 and K > 1 else 2 * C * S * K)
         del out, H, h
         torch.cuda.empty_cache()

@@ -3,9 +3,10 @@
 
 Compiles, on a checkout of BASE (git archive into a temporary directory) and on the working tree, with the Makefile's flags:
   smfft_amd/csrc/smfft_inst.hip   both objects (SMFFT_INST_PART = 1, 2 with tools/inst_flags.py) of all 8 lengths
-  smfft_amd/csrc/smfft_large.hip, smfft_large_real.hip, smfft_large_fir.hip, smfft_pfb.hip, smfft_pfb_real.hip, smfft_large_pfb.hip, smfft_pfb_spec.hip
-                                  the per-length objects of the seven add-on libraries, each with its <PREFIX>_FLAGS_<N> of the Makefile
-                                  (and the -I. of the five that include headers of that directory), where BASE has the file
+  smfft_amd/csrc/smfft_fir.hip    the main library's FIR object (all five lengths in one unit, the main library's flags)
+  smfft_amd/csrc/smfft_large.hip, smfft_large_real.hip, smfft_large_fir.hip, smfft_pfb.hip, smfft_pfb_real.hip, smfft_large_pfb.hip, smfft_pfb_spec.hip,
+  smfft_fir_real.hip              the per-length objects of the eight add-on libraries, each with its <PREFIX>_FLAGS_<N> of the Makefile
+                                  (and the -I. of the six that include headers of that directory), where BASE has the file
   examples/*.hip                  the files BASE has
 to device assembly (hipcc -S --cuda-device-only) and compares every kernel BASE has, text of its body and its .amdhsa descriptor,
 with the basic-block labels (.LBB<f>_<n>) and the function-local symbols renumbered in order of appearance.  A kernel whose text differs
@@ -32,7 +33,7 @@ SIZES = (32, 64, 128, 256, 512, 1024, 2048, 4096)
 ADDONS = (("smfft_large", "LARGE", (8192, 16384), False), ("smfft_large_real", "LARGE_REAL", (16384, 32768), False),
           ("smfft_large_fir", "LARGE_FIR", (8192, 16384), True), ("smfft_pfb", "PFB", (256, 512, 1024, 2048, 4096), True),
           ("smfft_pfb_real", "PFB_REAL", (256, 512, 1024, 2048, 4096), True), ("smfft_large_pfb", "LARGE_PFB", (8192, 16384), True),
-          ("smfft_pfb_spec", "PFB_SPEC", (256, 512, 1024, 2048, 4096), True))
+          ("smfft_pfb_spec", "PFB_SPEC", (256, 512, 1024, 2048, 4096), True), ("smfft_fir_real", "FIR_REAL", (256, 512, 1024, 2048, 4096), True))
 
 
 def addon_flags(prefix, n):
@@ -49,6 +50,8 @@ def units(tree):
     for n in SIZES:
         for part in (1, 2):
             out.append((f"smfft_inst_{n}_part{part}", "smfft_amd/csrc/smfft_inst.hip", part_flags(n, part) + [f"-DSMFFT_N={n}"]))
+    if os.path.exists(os.path.join(tree, "smfft_amd/csrc/smfft_fir.hip")):
+        out.append(("smfft_fir", "smfft_amd/csrc/smfft_fir.hip", []))
     for stem, prefix, sizes, local in ADDONS:
         rel = f"smfft_amd/csrc/{stem}.hip"
         if os.path.exists(os.path.join(tree, rel)):
