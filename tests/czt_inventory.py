@@ -1,0 +1,30 @@
+"""Every __global__ kernel that libsmfft_czt.so ships (batched chirp-z transforms of include/smfft_czt.h: one kernel per inner
+transform length M = 256 ... 4096), with the public call that reaches it and the GPU tests that compare it with fp64 ("tests"), run it
+on guarded buffers, at offset bases, in place and beyond 2^31 elements ("bounds") and probe it per output and in isolation ("probes").
+tests/test_sm_czt_cpu.py checks this list against the built library's kernels, with the rule of tests/test_kernel_inventory.py.  Names
+are the demangled kernel names without their parameter lists.
+
+There is no "host" kind here, for the reason tests/fir_real_inventory.py gives: the kernels' transforms are smfft::Engine<M, DIR, 1>,
+whose exchanges at M <= 4096 go through DPP / permlane lane operations; tests/hostsim emulates LDS, barriers and the schedule of a
+workgroup, not those cross-lane instructions."""
+
+SIZES = (256, 512, 1024, 2048, 4096)
+GPU = "tests/test_sm_czt_gpu.py::"
+# shapes (n, m) of the GPU tests that use M: n + m - 1 in (M / 2, M], or <= 256
+SHAPES = {256: ((1, 1), (128, 129)), 512: ((128, 130), (300, 200)), 1024: ((1000, 24), (1000, 25)), 2048: ((1000, 26), (2, 2047)),
+          4096: ((2048, 2048),)}
+
+
+def _entry(m):
+    return {
+        "call": f"smfft_czt_launch / smfft_czt_launch_tuned / smfft_czt_benchmark(n + m - 1 {'<=' if m == 256 else f'in {m // 2 + 1} ...'} {m})",
+        "tests": [GPU + "test_against_fp64", GPU + "test_grid_is_invisible"] + ([GPU + "test_grid_stride_loop"] if m in (256, 2048) else []),
+        "bounds": ([GPU + "test_bounds"] if m in (512, 2048) else [GPU + "test_against_fp64"])
+                  + ([GPU + "test_in_place"] if m in (512, 4096) else [])
+                  + ([GPU + "test_offsets_beyond_two_to_the_31"] if m == 2048 else []),
+        "probes": [GPU + "test_probe_impulses"] + ([GPU + "test_probe_tones"] if m == 4096 else [])
+                  + ([GPU + "test_probe_rows_are_isolated"] if m in (256, 4096) else []),
+    }
+
+
+KERNELS = {f"smfft::czt::czt_kernel<{m}>": _entry(m) for m in SIZES}
