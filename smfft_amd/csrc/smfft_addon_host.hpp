@@ -1,6 +1,7 @@
 // smfft_addon_host.hpp -- the host layer that the C ABI halves of the add-on libraries share (smfft_large.hip, smfft_large_real.hip,
 // smfft_large_fir.hip, smfft_pfb.hip, smfft_pfb_real.hip, smfft_large_pfb.hip, smfft_pfb_spec.hip, smfft_fir_real.hip; the FIR banks through
-// smfft_fir_host.hpp, which brings it to the main library's smfft_fir.hip as well): the compute units of the current device and the event-timed launch of the *_benchmark entry
+// smfft_fir_host.hpp, which brings it to the main library's smfft_fir.hip as well; the eight row libraries through smfft_rows_host.hpp,
+// which adds their grid rule, dispatch and entry point bodies): the compute units of the current device and the event-timed launch of the *_benchmark entry
 // points.  Host code only, and everything has internal linkage: each library keeps a cache of its own and exports nothing from here.
 #pragma once
 #include <hip/hip_runtime.h>

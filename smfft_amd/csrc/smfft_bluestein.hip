@@ -101,29 +101,17 @@ int launch_rows<SMFFT_BLUESTEIN_N>(const float2* in, float2* out, int n, long lo
 #else  // the C ABI
 #include <vector>
 
-#include "smfft_addon_host.hpp"
 #include "smfft_bluestein_tables.hpp"
+#include "smfft_rows_host.hpp"
 
 namespace {
-constexpr int kGridCap = 12288;     // smfft_fir_kernel.hpp kFirGridCap: workgroups along the tiles, grid-strided beyond
-
-// grid <= 0: the default, min(tiles, kGridCap)
-int dispatch(const void* in, void* out, int n, long long batch, const void* plan, int grid, hipStream_t stream) {
-    const int M = smfft::bluestein::fft_size(n);
-    if (grid <= 0) {
-        const long long tiles = (batch + 4096 / M - 1) / (4096 / M);
-        grid = (int)(tiles < kGridCap ? tiles : kGridCap);
-    }
-    const float2 *x = (const float2*)in, *p = (const float2*)plan;
-    float2* y = (float2*)out;
-    switch (M) {
-        case 256: return smfft::bluestein::launch_rows<256>(x, y, n, batch, p, grid, stream);
-        case 512: return smfft::bluestein::launch_rows<512>(x, y, n, batch, p, grid, stream);
-        case 1024: return smfft::bluestein::launch_rows<1024>(x, y, n, batch, p, grid, stream);
-        case 2048: return smfft::bluestein::launch_rows<2048>(x, y, n, batch, p, grid, stream);
-        case 4096: return smfft::bluestein::launch_rows<4096>(x, y, n, batch, p, grid, stream);
-    }
-    return -1;
+// the launch of `grid` workgroups (<= 0: the default) on `stream`
+auto dispatch(const void* in, void* out, int n, long long batch, const void* plan) {
+    return [=](int grid, hipStream_t stream) {
+        const int M = smfft::bluestein::fft_size(n);
+        grid = default_grid(M, batch, grid);
+        return dispatch_m(M, [&](auto m) { return smfft::bluestein::launch_rows<m()>((const float2*)in, (float2*)out, n, batch, (const float2*)plan, grid, stream); });
+    };
 }
 
 // -1: refused; 0: launch; 1: nothing to do.  No HIP call.
@@ -159,22 +147,15 @@ int smfft_bluestein_prepare(int n, int inverse, void* d_plan, void* hip_stream) 
 }
 
 int smfft_bluestein_launch(const void* d_in, void* d_out, int n, long long batch, const void* d_plan, void* hip_stream) {
-    const int chk = check(n, batch);
-    if (chk != 0) return chk < 0 ? -1 : 0;
-    return dispatch(d_in, d_out, n, batch, d_plan, 0, (hipStream_t)hip_stream);
+    return checked_launch(check(n, batch), dispatch(d_in, d_out, n, batch, d_plan), hip_stream);
 }
 
 int smfft_bluestein_launch_tuned(const void* d_in, void* d_out, int n, long long batch, const void* d_plan, void* hip_stream, int grid) {
-    const int chk = check(n, batch);
-    if (chk < 0 || grid < 1) return -1;
-    if (chk != 0) return 0;
-    return dispatch(d_in, d_out, n, batch, d_plan, grid, (hipStream_t)hip_stream);
+    return checked_launch_tuned(check(n, batch), dispatch(d_in, d_out, n, batch, d_plan), hip_stream, grid);
 }
 
 int smfft_bluestein_benchmark(const void* d_in, void* d_out, int n, long long batch, const void* d_plan, double* FFT_time) {
-    const int chk = check(n, batch);
-    if (chk != 0) return chk < 0 ? -1 : 0;
-    return timed_launch(FFT_time, [&] { return dispatch(d_in, d_out, n, batch, d_plan, 0, nullptr); });
+    return checked_benchmark(check(n, batch), dispatch(d_in, d_out, n, batch, d_plan), FFT_time);
 }
 
 }  // extern "C"

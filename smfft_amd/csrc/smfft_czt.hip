@@ -108,29 +108,17 @@ int launch_rows<SMFFT_CZT_N>(const float2* in, float2* out, int n, int m, long l
 #include <cmath>
 #include <vector>
 
-#include "smfft_addon_host.hpp"
 #include "smfft_czt_tables.hpp"
+#include "smfft_rows_host.hpp"
 
 namespace {
-constexpr int kGridCap = 12288;     // smfft_fir_kernel.hpp kFirGridCap: workgroups along the tiles, grid-strided beyond
-
-// grid <= 0: the default, min(tiles, kGridCap)
-int dispatch(const void* in, void* out, int n, int m, long long batch, const void* plan, int grid, hipStream_t stream) {
-    const int M = smfft::czt::fft_size(n, m);
-    if (grid <= 0) {
-        const long long tiles = (batch + 4096 / M - 1) / (4096 / M);
-        grid = (int)(tiles < kGridCap ? tiles : kGridCap);
-    }
-    const float2 *x = (const float2*)in, *p = (const float2*)plan;
-    float2* y = (float2*)out;
-    switch (M) {
-        case 256: return smfft::czt::launch_rows<256>(x, y, n, m, batch, p, grid, stream);
-        case 512: return smfft::czt::launch_rows<512>(x, y, n, m, batch, p, grid, stream);
-        case 1024: return smfft::czt::launch_rows<1024>(x, y, n, m, batch, p, grid, stream);
-        case 2048: return smfft::czt::launch_rows<2048>(x, y, n, m, batch, p, grid, stream);
-        case 4096: return smfft::czt::launch_rows<4096>(x, y, n, m, batch, p, grid, stream);
-    }
-    return -1;
+// the launch of `grid` workgroups (<= 0: the default) on `stream`
+auto dispatch(const void* in, void* out, int n, int m, long long batch, const void* plan) {
+    return [=](int grid, hipStream_t stream) {
+        const int M = smfft::czt::fft_size(n, m);
+        grid = default_grid(M, batch, grid);
+        return dispatch_m(M, [&](auto len) { return smfft::czt::launch_rows<len()>((const float2*)in, (float2*)out, n, m, batch, (const float2*)plan, grid, stream); });
+    };
 }
 
 // -1: refused; 0: launch; 1: nothing to do.  No HIP call.  In place only with m == n: rows of another length overlap their neighbours'.
@@ -168,22 +156,15 @@ int smfft_czt_prepare(int n, int m, double start, double step, void* d_plan, voi
 }
 
 int smfft_czt_launch(const void* d_in, void* d_out, int n, int m, long long batch, const void* d_plan, void* hip_stream) {
-    const int chk = check(d_in, d_out, n, m, batch);
-    if (chk != 0) return chk < 0 ? -1 : 0;
-    return dispatch(d_in, d_out, n, m, batch, d_plan, 0, (hipStream_t)hip_stream);
+    return checked_launch(check(d_in, d_out, n, m, batch), dispatch(d_in, d_out, n, m, batch, d_plan), hip_stream);
 }
 
 int smfft_czt_launch_tuned(const void* d_in, void* d_out, int n, int m, long long batch, const void* d_plan, void* hip_stream, int grid) {
-    const int chk = check(d_in, d_out, n, m, batch);
-    if (chk < 0 || grid < 1) return -1;
-    if (chk != 0) return 0;
-    return dispatch(d_in, d_out, n, m, batch, d_plan, grid, (hipStream_t)hip_stream);
+    return checked_launch_tuned(check(d_in, d_out, n, m, batch), dispatch(d_in, d_out, n, m, batch, d_plan), hip_stream, grid);
 }
 
 int smfft_czt_benchmark(const void* d_in, void* d_out, int n, int m, long long batch, const void* d_plan, double* FFT_time) {
-    const int chk = check(d_in, d_out, n, m, batch);
-    if (chk != 0) return chk < 0 ? -1 : 0;
-    return timed_launch(FFT_time, [&] { return dispatch(d_in, d_out, n, m, batch, d_plan, 0, nullptr); });
+    return checked_benchmark(check(d_in, d_out, n, m, batch), dispatch(d_in, d_out, n, m, batch, d_plan), FFT_time);
 }
 
 }  // extern "C"

@@ -29,8 +29,8 @@
 // beside the shipped library.
 //
 // Twiddles: W_n^k (k < M) and W_4n^k (k <= M) are rows built at compile time from the fp64-rounded first octant of W_32768
-// (smfft_twiddles_dct.inc, tools/gen_twiddles_dct.py) by exact symmetries, one row entry per element so that the lanes of a row read
-// consecutive addresses.  No v_sin / v_cos.
+// (smfft_twiddles_dct.inc, tools/gen_twiddles_dct.py) by exact symmetries (smfft_rows.hpp, which the four libraries of real rows on a
+// half-length transform share), one row entry per element so that the lanes of a row read consecutive addresses.  No v_sin / v_cos.
 //
 // In place (d_out == d_in) is served: every value a workgroup loads from a row is consumed in front of the first exchange behind the
 // loads -- the pass of the quads' second half through LDS, type III's partner exchange, or the transform's own; a barrier where a row
@@ -58,6 +58,7 @@ int launch_rows(const float* in, float* out, long long batch, int type, int sine
 
 #ifdef SMFFT_DCT_N
 #include "smfft_fir_kernel.hpp"
+#include "smfft_rows.hpp"
 
 // 1: 16-byte row accesses and a pass through the row's LDS region; 0: 4-byte row accesses at stride four
 #ifndef SMFFT_DCT_STAGED
@@ -82,16 +83,7 @@ int launch_rows(const float* in, float* out, long long batch, int type, int sine
 namespace smfft {
 namespace dct {
 
-static constexpr TwiddleValue octant_32768[4097] = {
-#include "smfft/smfft_twiddles_dct.inc"
-};
-
-// (cos, sin)(2 pi m / 32768), 0 <= m < 16384, from the octant: exact symmetries, so every entry is an fp64 value rounded once
-constexpr TwiddleValue w32768(int m) {
-    const int q = m / 4096, r = m % 4096;
-    const TwiddleValue a = octant_32768[r], b = octant_32768[4096 - r];
-    return q == 0 ? TwiddleValue{a.x, a.y} : q == 1 ? TwiddleValue{b.y, b.x} : q == 2 ? TwiddleValue{-a.y, a.x} : TwiddleValue{-b.x, b.y};
-}
+using rows::w32768, rows::row_entry, rows::per_tile, rows::row_quad;
 
 // the twiddle rows of n = 2 M points as (cos, sin), that is the CONJUGATES of W_n^k and W_4n^k
 template <int M>
@@ -106,49 +98,11 @@ struct Rows {
 template <int M>
 static __device__ const Rows<M> rows = Rows<M>();
 
-__device__ __forceinline__ float2 row_entry(const TwiddleValue* p) {
-    const TwiddleValue v = *p;
-    return make_float2(v.x, v.y);
-}
-
-// v, as a value the compiler takes for new in every tile: the twiddle loads indexed with it stay inside the tile loop, where their
-// registers are free again behind the use, and are not kept across the loop (thirty-two to forty-eight float2 per thread: with them
-// resident the kernels need more than 256 VGPRs, one wave per SIMD)
-__device__ __forceinline__ int per_tile(int v) {
-    asm volatile("" : "+v"(v));
-    return v;
-}
-
 // one float, or four consecutive floats at 4-byte alignment, with the policies above
-typedef float row_quad __attribute__((ext_vector_type(4), aligned(4)));
-__device__ __forceinline__ float gload1(const float* p) {
-#if SMFFT_DCT_NT_LOAD1
-    return __builtin_nontemporal_load(p);
-#else
-    return *p;
-#endif
-}
-__device__ __forceinline__ void gstore1(float* p, float v) {
-#if SMFFT_DCT_NT_STORE1
-    __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
-}
-__device__ __forceinline__ row_quad gload4(const float* p) {
-#if SMFFT_DCT_NT_LOAD4
-    return __builtin_nontemporal_load(reinterpret_cast<const row_quad*>(p));
-#else
-    return *reinterpret_cast<const row_quad*>(p);
-#endif
-}
-__device__ __forceinline__ void gstore4(float* p, row_quad v) {
-#if SMFFT_DCT_NT_STORE4
-    __builtin_nontemporal_store(v, reinterpret_cast<row_quad*>(p));
-#else
-    *reinterpret_cast<row_quad*>(p) = v;
-#endif
-}
+__device__ __forceinline__ float gload1(const float* p) { return rows::gload1<SMFFT_DCT_NT_LOAD1 != 0>(p); }
+__device__ __forceinline__ void gstore1(float* p, float v) { rows::gstore1<SMFFT_DCT_NT_STORE1 != 0>(p, v); }
+__device__ __forceinline__ row_quad gload4(const float* p) { return rows::gload4<SMFFT_DCT_NT_LOAD4 != 0>(p); }
+__device__ __forceinline__ void gstore4(float* p, row_quad v) { rows::gstore4<SMFFT_DCT_NT_STORE4 != 0>(p, v); }
 
 // out[r n + .] = DCT-II (sine == 0) or DST-II of in[r n + .], n = 2 M.  in and out may be the same buffer: no __restrict__.
 template <int M>
@@ -329,71 +283,42 @@ int launch_rows<SMFFT_DCT_N>(const float* in, float* out, long long batch, int t
 }  // namespace smfft
 
 #else  // the C ABI
-#include <cstdint>
-
-#include "smfft_addon_host.hpp"
+#include "smfft_rows_host.hpp"
 
 namespace {
-constexpr int kGridCap = 12288;     // smfft_fir_kernel.hpp kFirGridCap: workgroups along the tiles, grid-strided beyond
-
-// M = n / 2 for n a power of two in 512 ... 8192; -1 otherwise
-int fft_size(int n) {
-    if (n < 512 || n > 8192 || (n & (n - 1)) != 0) return -1;
-    return n / 2;
-}
-
-// grid <= 0: the default, min(tiles, kGridCap)
-int dispatch(const void* in, void* out, int n, long long batch, int type, int sine, int grid, hipStream_t stream) {
-    const int M = fft_size(n);
-    if (grid <= 0) {
-        const long long tiles = (batch + 4096 / M - 1) / (4096 / M);
-        grid = (int)(tiles < kGridCap ? tiles : kGridCap);
-    }
-    const float* x = (const float*)in;
-    float* y = (float*)out;
-    sine = sine != 0;
-    switch (M) {
-        case 256: return smfft::dct::launch_rows<256>(x, y, batch, type, sine, grid, stream);
-        case 512: return smfft::dct::launch_rows<512>(x, y, batch, type, sine, grid, stream);
-        case 1024: return smfft::dct::launch_rows<1024>(x, y, batch, type, sine, grid, stream);
-        case 2048: return smfft::dct::launch_rows<2048>(x, y, batch, type, sine, grid, stream);
-        case 4096: return smfft::dct::launch_rows<4096>(x, y, batch, type, sine, grid, stream);
-    }
-    return -1;
+// the launch of `grid` workgroups (<= 0: the default) on `stream`
+auto dispatch(const void* in, void* out, int n, long long batch, int type, int sine) {
+    return [=](int grid, hipStream_t stream) {
+        const int M = half_length_fft_size(n);
+        grid = default_grid(M, batch, grid);
+        return dispatch_m(M, [&](auto m) { return smfft::dct::launch_rows<m()>((const float*)in, (float*)out, batch, type, sine != 0, grid, stream); });
+    };
 }
 
 // -1: refused; 0: launch; 1: nothing to do.  No HIP call.  The output is the input (in place) or does not overlap it.
 int check(const void* in, const void* out, int n, long long batch, int type) {
-    if (fft_size(n) < 0 || (type != 2 && type != 3) || batch < 0) return -1;
+    if (half_length_fft_size(n) < 0 || (type != 2 && type != 3) || batch < 0) return -1;
     if (batch == 0) return 1;
-    const std::uintptr_t a = (std::uintptr_t)in, b = (std::uintptr_t)out;
-    const unsigned long long bytes = (unsigned long long)batch * (unsigned long long)n * sizeof(float);
-    if (a != b && (a < b ? b - a : a - b) < bytes) return -1;
+    const unsigned long long count = (unsigned long long)batch * (unsigned long long)n;
+    if (in != out && overlap(in, count, out, count)) return -1;
     return 0;
 }
 }  // namespace
 
 extern "C" {
 
-int smfft_dct_fft_size(int n) { return fft_size(n); }
+int smfft_dct_fft_size(int n) { return half_length_fft_size(n); }
 
 int smfft_dct_launch(const void* d_in, void* d_out, int n, long long batch, int type, int sine, void* hip_stream) {
-    const int chk = check(d_in, d_out, n, batch, type);
-    if (chk != 0) return chk < 0 ? -1 : 0;
-    return dispatch(d_in, d_out, n, batch, type, sine, 0, (hipStream_t)hip_stream);
+    return checked_launch(check(d_in, d_out, n, batch, type), dispatch(d_in, d_out, n, batch, type, sine), hip_stream);
 }
 
 int smfft_dct_launch_tuned(const void* d_in, void* d_out, int n, long long batch, int type, int sine, void* hip_stream, int grid) {
-    const int chk = check(d_in, d_out, n, batch, type);
-    if (chk < 0 || grid < 1) return -1;
-    if (chk != 0) return 0;
-    return dispatch(d_in, d_out, n, batch, type, sine, grid, (hipStream_t)hip_stream);
+    return checked_launch_tuned(check(d_in, d_out, n, batch, type), dispatch(d_in, d_out, n, batch, type, sine), hip_stream, grid);
 }
 
 int smfft_dct_benchmark(const void* d_in, void* d_out, int n, long long batch, int type, int sine, double* FFT_time) {
-    const int chk = check(d_in, d_out, n, batch, type);
-    if (chk != 0) return chk < 0 ? -1 : 0;
-    return timed_launch(FFT_time, [&] { return dispatch(d_in, d_out, n, batch, type, sine, 0, nullptr); });
+    return checked_benchmark(check(d_in, d_out, n, batch, type), dispatch(d_in, d_out, n, batch, type, sine), FFT_time);
 }
 
 }  // extern "C"

@@ -22,8 +22,8 @@
 // first store; it takes 1.1 ... 1.3 times as long on an MI355X (tools/ab_hilbert.py).
 //
 // Twiddles: W_n^k (k < M) is the row that the DCT kernels build at compile time from the fp64-rounded first octant of W_32768
-// (smfft_twiddles_dct.inc) by exact symmetries, built here a second time from the same table so that smfft_dct.hip and its ten kernels
-// stay as they are.  No v_sin / v_cos.
+// (smfft_twiddles_dct.inc) by exact symmetries (smfft_rows.hpp), in an object of this library's own so that smfft_dct.hip and its ten
+// kernels stay as they are.  No v_sin / v_cos.
 //
 // In place (d_out == d_in), kinds 0 and 2: every value a workgroup loads from a row is consumed in front of the first exchange behind
 // the loads (the forward transform's own; a barrier where a row spans waves) and the stores come behind the inverse transform; rows
@@ -47,6 +47,7 @@ int launch_rows(const float* in, float* out, long long batch, int kind, int grid
 
 #ifdef SMFFT_HILBERT_N
 #include "smfft_fir_kernel.hpp"
+#include "smfft_rows.hpp"
 
 // kinds 1 and 2: 1 keeps x in registers across the transforms, 0 loads it a second time in front of the store.  Both stay under 256
 // VGPRs without scratch; kept ships by measurement (the second load costs 10 ... 32 % of the launch)
@@ -64,16 +65,7 @@ int launch_rows(const float* in, float* out, long long batch, int kind, int grid
 namespace smfft {
 namespace hilbert {
 
-static constexpr TwiddleValue octant_32768[4097] = {
-#include "smfft/smfft_twiddles_dct.inc"
-};
-
-// (cos, sin)(2 pi m / 32768), 0 <= m < 16384, from the octant: exact symmetries, so every entry is an fp64 value rounded once
-constexpr TwiddleValue w32768(int m) {
-    const int q = m / 4096, r = m % 4096;
-    const TwiddleValue a = octant_32768[r], b = octant_32768[4096 - r];
-    return q == 0 ? TwiddleValue{a.x, a.y} : q == 1 ? TwiddleValue{b.y, b.x} : q == 2 ? TwiddleValue{-a.y, a.x} : TwiddleValue{-b.x, b.y};
-}
+using rows::w32768, rows::row_entry, rows::per_tile, rows::row_quad;
 
 // the twiddle row of n = 2 M points as (cos, sin)(2 pi k / n), that is the CONJUGATE of W_n^k
 template <int M>
@@ -86,49 +78,16 @@ struct Rows {
 template <int M>
 static __device__ const Rows<M> rows = Rows<M>();
 
-__device__ __forceinline__ float2 row_entry(const TwiddleValue* p) {
-    const TwiddleValue v = *p;
-    return make_float2(v.x, v.y);
-}
-
-// v, as a value the compiler takes for new in every tile: the twiddle loads indexed with it stay inside the tile loop (smfft_dct.hip)
-__device__ __forceinline__ int per_tile(int v) {
-    asm volatile("" : "+v"(v));
-    return v;
-}
-
 // two or four consecutive floats at 4-byte alignment, with the policies above
-typedef float row_pair __attribute__((ext_vector_type(2), aligned(4)));
-typedef float row_quad __attribute__((ext_vector_type(4), aligned(4)));
-__device__ __forceinline__ float2 gload2(const float* p) {
-#if SMFFT_HILBERT_NT_LOAD
-    const row_pair v = __builtin_nontemporal_load(reinterpret_cast<const row_pair*>(p));
-#else
-    const row_pair v = *reinterpret_cast<const row_pair*>(p);
-#endif
-    return make_float2(v.x, v.y);
-}
+__device__ __forceinline__ float2 gload2(const float* p) { return rows::gload2<SMFFT_HILBERT_NT_LOAD != 0>(p); }
+__device__ __forceinline__ void gstore2(float* p, float a, float b) { rows::gstore2<SMFFT_HILBERT_NT_STORE != 0>(p, a, b); }
+__device__ __forceinline__ void gstore4(float* p, row_quad v) { rows::gstore4<SMFFT_HILBERT_NT_STORE != 0>(p, v); }
 // a loaded pair as two values of their own.  Where the pairs are kept across the transforms (x below), the compiler otherwise holds
 // them as the vectors they were loaded as and runs the forward transform's first additions on those: thirty v_pk_add_f32 per thread,
 // half rate on gfx950, whatever -fno-slp-vectorize says
 __device__ __forceinline__ float2 taken_apart(float2 v) {
     asm volatile("" : "+v"(v.x), "+v"(v.y));
     return v;
-}
-__device__ __forceinline__ void gstore2(float* p, float a, float b) {
-    const row_pair v = {a, b};
-#if SMFFT_HILBERT_NT_STORE
-    __builtin_nontemporal_store(v, reinterpret_cast<row_pair*>(p));
-#else
-    *reinterpret_cast<row_pair*>(p) = v;
-#endif
-}
-__device__ __forceinline__ void gstore4(float* p, row_quad v) {
-#if SMFFT_HILBERT_NT_STORE
-    __builtin_nontemporal_store(v, reinterpret_cast<row_quad*>(p));
-#else
-    *reinterpret_cast<row_quad*>(p) = v;
-#endif
 }
 
 // KIND 0: out[r n + .] = H(in[r n + .]); 1: out[2 (r n + j)], out[2 (r n + j) + 1] = in[r n + j], H(in[r n + .])[j];
@@ -220,73 +179,44 @@ int launch_rows<SMFFT_HILBERT_N>(const float* in, float* out, long long batch, i
 }  // namespace smfft
 
 #else  // the C ABI
-#include <cstdint>
-
-#include "smfft_addon_host.hpp"
+#include "smfft_rows_host.hpp"
 
 namespace {
-constexpr int kGridCap = 12288;     // smfft_fir_kernel.hpp kFirGridCap: workgroups along the tiles, grid-strided beyond
-
-// M = n / 2 for n a power of two in 512 ... 8192; -1 otherwise
-int fft_size(int n) {
-    if (n < 512 || n > 8192 || (n & (n - 1)) != 0) return -1;
-    return n / 2;
-}
-
-// grid <= 0: the default, min(tiles, kGridCap)
-int dispatch(const void* in, void* out, int n, long long batch, int kind, int grid, hipStream_t stream) {
-    const int M = fft_size(n);
-    if (grid <= 0) {
-        const long long tiles = (batch + 4096 / M - 1) / (4096 / M);
-        grid = (int)(tiles < kGridCap ? tiles : kGridCap);
-    }
-    const float* x = (const float*)in;
-    float* y = (float*)out;
-    switch (M) {
-        case 256: return smfft::hilbert::launch_rows<256>(x, y, batch, kind, grid, stream);
-        case 512: return smfft::hilbert::launch_rows<512>(x, y, batch, kind, grid, stream);
-        case 1024: return smfft::hilbert::launch_rows<1024>(x, y, batch, kind, grid, stream);
-        case 2048: return smfft::hilbert::launch_rows<2048>(x, y, batch, kind, grid, stream);
-        case 4096: return smfft::hilbert::launch_rows<4096>(x, y, batch, kind, grid, stream);
-    }
-    return -1;
+// the launch of `grid` workgroups (<= 0: the default) on `stream`
+auto dispatch(const void* in, void* out, int n, long long batch, int kind) {
+    return [=](int grid, hipStream_t stream) {
+        const int M = half_length_fft_size(n);
+        grid = default_grid(M, batch, grid);
+        return dispatch_m(M, [&](auto m) { return smfft::hilbert::launch_rows<m()>((const float*)in, (float*)out, batch, kind, grid, stream); });
+    };
 }
 
 // -1: refused; 0: launch; 1: nothing to do.  No HIP call.  Kinds 0 and 2: the output is the input (in place) or does not overlap it;
 // kind 1: it does not overlap it
 int check(const void* in, const void* out, int n, long long batch, int kind) {
-    if (fft_size(n) < 0 || kind < 0 || kind > 2 || batch < 0) return -1;
+    if (half_length_fft_size(n) < 0 || kind < 0 || kind > 2 || batch < 0) return -1;
     if (batch == 0) return 1;
-    const std::uintptr_t a = (std::uintptr_t)in, b = (std::uintptr_t)out;
-    const unsigned long long in_bytes = (unsigned long long)batch * (unsigned long long)n * sizeof(float);
-    const unsigned long long out_bytes = kind == 1 ? 2 * in_bytes : in_bytes;
-    if (a == b) return kind == 1 ? -1 : 0;
-    if (a < b ? b - a < in_bytes : a - b < out_bytes) return -1;
+    const unsigned long long ins = (unsigned long long)batch * (unsigned long long)n;
+    if (in == out) return kind == 1 ? -1 : 0;
+    if (overlap(in, ins, out, kind == 1 ? 2 * ins : ins)) return -1;
     return 0;
 }
 }  // namespace
 
 extern "C" {
 
-int smfft_hilbert_fft_size(int n) { return fft_size(n); }
+int smfft_hilbert_fft_size(int n) { return half_length_fft_size(n); }
 
 int smfft_hilbert_launch(const void* d_in, void* d_out, int n, long long batch, int kind, void* hip_stream) {
-    const int chk = check(d_in, d_out, n, batch, kind);
-    if (chk != 0) return chk < 0 ? -1 : 0;
-    return dispatch(d_in, d_out, n, batch, kind, 0, (hipStream_t)hip_stream);
+    return checked_launch(check(d_in, d_out, n, batch, kind), dispatch(d_in, d_out, n, batch, kind), hip_stream);
 }
 
 int smfft_hilbert_launch_tuned(const void* d_in, void* d_out, int n, long long batch, int kind, void* hip_stream, int grid) {
-    const int chk = check(d_in, d_out, n, batch, kind);
-    if (chk < 0 || grid < 1) return -1;
-    if (chk != 0) return 0;
-    return dispatch(d_in, d_out, n, batch, kind, grid, (hipStream_t)hip_stream);
+    return checked_launch_tuned(check(d_in, d_out, n, batch, kind), dispatch(d_in, d_out, n, batch, kind), hip_stream, grid);
 }
 
 int smfft_hilbert_benchmark(const void* d_in, void* d_out, int n, long long batch, int kind, double* FFT_time) {
-    const int chk = check(d_in, d_out, n, batch, kind);
-    if (chk != 0) return chk < 0 ? -1 : 0;
-    return timed_launch(FFT_time, [&] { return dispatch(d_in, d_out, n, batch, kind, 0, nullptr); });
+    return checked_benchmark(check(d_in, d_out, n, batch, kind), dispatch(d_in, d_out, n, batch, kind), FFT_time);
 }
 
 }  // extern "C"

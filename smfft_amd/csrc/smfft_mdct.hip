@@ -27,7 +27,7 @@
 //
 // Twiddles: exp(-i pi k / n) = W_32768^{k 16384 / n} and exp(-i pi (4p+1) / (4n)) = W_65536^{(4p+1) 8192 / n} are rows built at compile
 // time, one entry per element so that the lanes of a row read consecutive addresses, from the fp64-rounded first octant of W_32768
-// (smfft_twiddles_dct.inc) and, for the odd indices that n = 8192 needs, from the odd entries of the first octant of W_65536
+// (smfft_twiddles_dct.inc through smfft_rows.hpp) and, for the odd indices that n = 8192 needs, from the odd entries of the first octant of W_65536
 // (smfft_twiddles_mdct.inc, tools/gen_twiddles_mdct.py), extended by exact symmetries.  No v_sin / v_cos.
 //
 // In place (dct4, d_out == d_in) is served: every value a workgroup loads from a row is in LDS or in registers in front of the first
@@ -59,6 +59,7 @@ int launch_imdct(const float* in, float* out, const float* window, long long bat
 
 #ifdef SMFFT_MDCT_N
 #include "smfft_fir_kernel.hpp"
+#include "smfft_rows.hpp"
 
 // 1: 16-byte row accesses and a pass through the row's LDS region; 0: 4-byte row accesses at stride two
 #ifndef SMFFT_MDCT_STAGED
@@ -82,19 +83,11 @@ int launch_imdct(const float* in, float* out, const float* window, long long bat
 namespace smfft {
 namespace mdct {
 
-static constexpr TwiddleValue octant_32768[4097] = {
-#include "smfft/smfft_twiddles_dct.inc"
-};
+using rows::w32768, rows::row_entry, rows::per_tile, rows::row_quad;
+
 static constexpr TwiddleValue odd_octant_65536[4096] = {
 #include "smfft/smfft_twiddles_mdct.inc"
 };
-
-// (cos, sin)(2 pi m / 32768), 0 <= m < 16384, from the octant: exact symmetries, so every entry is an fp64 value rounded once
-constexpr TwiddleValue w32768(int m) {
-    const int q = m / 4096, r = m % 4096;
-    const TwiddleValue a = octant_32768[r], b = octant_32768[4096 - r];
-    return q == 0 ? TwiddleValue{a.x, a.y} : q == 1 ? TwiddleValue{b.y, b.x} : q == 2 ? TwiddleValue{-a.y, a.x} : TwiddleValue{-b.x, b.y};
-}
 
 // (cos, sin)(2 pi m / 65536), 0 <= m < 16384: the even m are entries of W_32768, the odd ones below pi / 4 are the table's, and
 // (cos, sin)(pi / 2 - t) = (sin, cos)(t) takes the odd ones beyond it to those
@@ -118,49 +111,13 @@ struct Rows {
 template <int M>
 static __device__ const Rows<M> rows = Rows<M>();
 
-__device__ __forceinline__ float2 row_entry(const TwiddleValue* p) {
-    const TwiddleValue v = *p;
-    return make_float2(v.x, v.y);
-}
-
-// v, as a value the compiler takes for new in every tile: the twiddle loads indexed with it stay inside the tile loop (smfft_dct.hip)
-__device__ __forceinline__ int per_tile(int v) {
-    asm volatile("" : "+v"(v));
-    return v;
-}
-
 // one float, or four consecutive floats at 4-byte alignment, with the policies above
-typedef float row_quad __attribute__((ext_vector_type(4), aligned(4)));
-__device__ __forceinline__ float gload1(const float* p) {
-#if SMFFT_MDCT_NT_LOAD1
-    return __builtin_nontemporal_load(p);
-#else
-    return *p;
-#endif
-}
-__device__ __forceinline__ void gstore1(float* p, float v) {
-#if SMFFT_MDCT_NT_STORE1
-    __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
-}
-__device__ __forceinline__ row_quad gload4(const float* p) {
-#if SMFFT_MDCT_NT_LOAD4
-    return __builtin_nontemporal_load(reinterpret_cast<const row_quad*>(p));
-#else
-    return *reinterpret_cast<const row_quad*>(p);
-#endif
-}
-__device__ __forceinline__ void gstore4(float* p, row_quad v) {
-#if SMFFT_MDCT_NT_STORE4
-    __builtin_nontemporal_store(v, reinterpret_cast<row_quad*>(p));
-#else
-    *reinterpret_cast<row_quad*>(p) = v;
-#endif
-}
+__device__ __forceinline__ float gload1(const float* p) { return rows::gload1<SMFFT_MDCT_NT_LOAD1 != 0>(p); }
+__device__ __forceinline__ void gstore1(float* p, float v) { rows::gstore1<SMFFT_MDCT_NT_STORE1 != 0>(p, v); }
+__device__ __forceinline__ row_quad gload4(const float* p) { return rows::gload4<SMFFT_MDCT_NT_LOAD4 != 0>(p); }
+__device__ __forceinline__ void gstore4(float* p, row_quad v) { rows::gstore4<SMFFT_MDCT_NT_STORE4 != 0>(p, v); }
 // the window: plain loads, every frame reads it
-__device__ __forceinline__ row_quad wload4(const float* p) { return *reinterpret_cast<const row_quad*>(p); }
+__device__ __forceinline__ row_quad wload4(const float* p) { return rows::gload4<false>(p); }
 
 // two consecutive floats of a row's LDS region, at an even float index
 __device__ __forceinline__ float2 lds_pair(const float* fl, int i) { return *reinterpret_cast<const float2*>(fl + i); }
@@ -533,74 +490,43 @@ int launch_imdct<SMFFT_MDCT_N>(const float* in, float* out, const float* window,
 }  // namespace smfft
 
 #else  // the C ABI
-#include <cstdint>
-
-#include "smfft_addon_host.hpp"
+#include "smfft_rows_host.hpp"
 
 namespace {
-constexpr int kGridCap = 12288;     // smfft_fir_kernel.hpp kFirGridCap: workgroups along the tiles, grid-strided beyond
 constexpr unsigned long long kMaxElements = 1ull << 60;      // of a buffer: keeps the byte counts below inside 64 bits
 
-// M = n / 2 for n a power of two in 512 ... 8192; -1 otherwise
-int fft_size(int n) {
-    if (n < 512 || n > 8192 || (n & (n - 1)) != 0) return -1;
-    return n / 2;
+// the launches of `grid` workgroups (<= 0: the default) on `stream`
+auto dispatch_dct4(const void* in, void* out, int n, long long batch, int sine) {
+    return [=](int grid, hipStream_t stream) {
+        const int M = half_length_fft_size(n);
+        grid = default_grid(M, batch, grid);
+        return dispatch_m(M, [&](auto m) { return smfft::mdct::launch_dct4<m()>((const float*)in, (float*)out, batch, sine != 0, grid, stream); });
+    };
 }
 
-// grid <= 0: the default, min(tiles, kGridCap)
-int default_grid(int M, long long rows, int grid) {
-    if (grid > 0) return grid;
-    const long long tiles = (rows + 4096 / M - 1) / (4096 / M);
-    return (int)(tiles < kGridCap ? tiles : kGridCap);
+auto dispatch_mdct(const void* in, void* out, const void* window, int N, long long streams, long long frames, long long hop, long long stream_stride) {
+    return [=](int grid, hipStream_t stream) {
+        const int M = half_length_fft_size(N);
+        const long long total = streams * frames;
+        grid = default_grid(M, total, grid);
+        return dispatch_m(M, [&](auto m) {
+            return smfft::mdct::launch_mdct<m()>((const float*)in, (float*)out, (const float*)window, total, frames, hop, stream_stride, grid, stream);
+        });
+    };
 }
 
-// do [a, a + na floats) and [b, b + nb floats) share a byte
-bool overlap(const void* a, unsigned long long na, const void* b, unsigned long long nb) {
-    const std::uintptr_t pa = (std::uintptr_t)a, pb = (std::uintptr_t)b;
-    return pa < pb ? pb - pa < na * sizeof(float) : pa - pb < nb * sizeof(float);
-}
-
-#define SMFFT_MDCT_DISPATCH(M, call)                    \
-    switch (M) {                                        \
-        case 256: return smfft::mdct::call(256);        \
-        case 512: return smfft::mdct::call(512);        \
-        case 1024: return smfft::mdct::call(1024);      \
-        case 2048: return smfft::mdct::call(2048);      \
-        case 4096: return smfft::mdct::call(4096);      \
-    }                                                   \
-    return -1
-
-int dispatch_dct4(const void* in, void* out, int n, long long batch, int sine, int grid, hipStream_t stream) {
-    const int M = fft_size(n);
-    grid = default_grid(M, batch, grid);
-    sine = sine != 0;
-#define SMFFT_MDCT_CALL(m) launch_dct4<m>((const float*)in, (float*)out, batch, sine, grid, stream)
-    SMFFT_MDCT_DISPATCH(M, SMFFT_MDCT_CALL);
-#undef SMFFT_MDCT_CALL
-}
-
-int dispatch_mdct(const void* in, void* out, const void* window, int N, long long streams, long long frames, long long hop, long long stream_stride,
-                  int grid, hipStream_t stream) {
-    const int M = fft_size(N);
-    const long long total = streams * frames;
-    grid = default_grid(M, total, grid);
-#define SMFFT_MDCT_CALL(m) launch_mdct<m>((const float*)in, (float*)out, (const float*)window, total, frames, hop, stream_stride, grid, stream)
-    SMFFT_MDCT_DISPATCH(M, SMFFT_MDCT_CALL);
-#undef SMFFT_MDCT_CALL
-}
-
-int dispatch_imdct(const void* in, void* out, const void* window, int N, long long batch, int grid, hipStream_t stream) {
-    const int M = fft_size(N);
-    grid = default_grid(M, batch, grid);
-#define SMFFT_MDCT_CALL(m) launch_imdct<m>((const float*)in, (float*)out, (const float*)window, batch, grid, stream)
-    SMFFT_MDCT_DISPATCH(M, SMFFT_MDCT_CALL);
-#undef SMFFT_MDCT_CALL
+auto dispatch_imdct(const void* in, void* out, const void* window, int N, long long batch) {
+    return [=](int grid, hipStream_t stream) {
+        const int M = half_length_fft_size(N);
+        grid = default_grid(M, batch, grid);
+        return dispatch_m(M, [&](auto m) { return smfft::mdct::launch_imdct<m()>((const float*)in, (float*)out, (const float*)window, batch, grid, stream); });
+    };
 }
 
 // -1: refused; 0: launch; 1: nothing to do.  No HIP call.
 // dct4: the output is the input (in place) or does not overlap it
 int check_dct4(const void* in, const void* out, int n, long long batch) {
-    if (fft_size(n) < 0 || batch < 0) return -1;
+    if (half_length_fft_size(n) < 0 || batch < 0) return -1;
     if (batch == 0) return 1;
     if ((unsigned long long)batch > kMaxElements / (unsigned)n) return -1;
     const unsigned long long count = (unsigned long long)batch * (unsigned)n;
@@ -610,7 +536,7 @@ int check_dct4(const void* in, const void* out, int n, long long batch) {
 
 // mdct: the output overlaps neither the range of the frames nor the window
 int check_mdct(const void* in, const void* out, const void* window, int N, long long streams, long long frames, long long hop, long long stream_stride) {
-    if (fft_size(N) < 0 || streams < 0 || frames < 0 || hop < 1 || stream_stride < 1) return -1;
+    if (half_length_fft_size(N) < 0 || streams < 0 || frames < 0 || hop < 1 || stream_stride < 1) return -1;
     if (streams == 0 || frames == 0) return 1;
     const unsigned __int128 total = (unsigned __int128)streams * (unsigned __int128)frames;
     const unsigned __int128 extent = (unsigned __int128)(streams - 1) * (unsigned __int128)stream_stride
@@ -624,7 +550,7 @@ int check_mdct(const void* in, const void* out, const void* window, int N, long 
 
 // imdct: the output overlaps neither the input nor the window
 int check_imdct(const void* in, const void* out, const void* window, int N, long long batch) {
-    if (fft_size(N) < 0 || batch < 0) return -1;
+    if (half_length_fft_size(N) < 0 || batch < 0) return -1;
     if (batch == 0) return 1;
     if ((unsigned long long)batch > kMaxElements / (2u * (unsigned)N)) return -1;
     const unsigned long long ins = (unsigned long long)batch * (unsigned)N;
@@ -636,63 +562,45 @@ int check_imdct(const void* in, const void* out, const void* window, int N, long
 
 extern "C" {
 
-int smfft_mdct_fft_size(int n) { return fft_size(n); }
+int smfft_mdct_fft_size(int n) { return half_length_fft_size(n); }
 
 int smfft_dct4_launch(const void* d_in, void* d_out, int n, long long batch, int sine, void* hip_stream) {
-    const int chk = check_dct4(d_in, d_out, n, batch);
-    if (chk != 0) return chk < 0 ? -1 : 0;
-    return dispatch_dct4(d_in, d_out, n, batch, sine, 0, (hipStream_t)hip_stream);
+    return checked_launch(check_dct4(d_in, d_out, n, batch), dispatch_dct4(d_in, d_out, n, batch, sine), hip_stream);
 }
 
 int smfft_dct4_launch_tuned(const void* d_in, void* d_out, int n, long long batch, int sine, void* hip_stream, int grid) {
-    const int chk = check_dct4(d_in, d_out, n, batch);
-    if (chk < 0 || grid < 1) return -1;
-    if (chk != 0) return 0;
-    return dispatch_dct4(d_in, d_out, n, batch, sine, grid, (hipStream_t)hip_stream);
+    return checked_launch_tuned(check_dct4(d_in, d_out, n, batch), dispatch_dct4(d_in, d_out, n, batch, sine), hip_stream, grid);
 }
 
 int smfft_dct4_benchmark(const void* d_in, void* d_out, int n, long long batch, int sine, double* FFT_time) {
-    const int chk = check_dct4(d_in, d_out, n, batch);
-    if (chk != 0) return chk < 0 ? -1 : 0;
-    return timed_launch(FFT_time, [&] { return dispatch_dct4(d_in, d_out, n, batch, sine, 0, nullptr); });
+    return checked_benchmark(check_dct4(d_in, d_out, n, batch), dispatch_dct4(d_in, d_out, n, batch, sine), FFT_time);
 }
 
 int smfft_mdct_launch(const void* d_in, void* d_out, const void* d_window, int N, long long streams, long long frames, long long hop, long long stream_stride, void* hip_stream) {
-    const int chk = check_mdct(d_in, d_out, d_window, N, streams, frames, hop, stream_stride);
-    if (chk != 0) return chk < 0 ? -1 : 0;
-    return dispatch_mdct(d_in, d_out, d_window, N, streams, frames, hop, stream_stride, 0, (hipStream_t)hip_stream);
+    return checked_launch(check_mdct(d_in, d_out, d_window, N, streams, frames, hop, stream_stride),
+                          dispatch_mdct(d_in, d_out, d_window, N, streams, frames, hop, stream_stride), hip_stream);
 }
 
 int smfft_mdct_launch_tuned(const void* d_in, void* d_out, const void* d_window, int N, long long streams, long long frames, long long hop, long long stream_stride, void* hip_stream, int grid) {
-    const int chk = check_mdct(d_in, d_out, d_window, N, streams, frames, hop, stream_stride);
-    if (chk < 0 || grid < 1) return -1;
-    if (chk != 0) return 0;
-    return dispatch_mdct(d_in, d_out, d_window, N, streams, frames, hop, stream_stride, grid, (hipStream_t)hip_stream);
+    return checked_launch_tuned(check_mdct(d_in, d_out, d_window, N, streams, frames, hop, stream_stride),
+                                dispatch_mdct(d_in, d_out, d_window, N, streams, frames, hop, stream_stride), hip_stream, grid);
 }
 
 int smfft_mdct_benchmark(const void* d_in, void* d_out, const void* d_window, int N, long long streams, long long frames, long long hop, long long stream_stride, double* FFT_time) {
-    const int chk = check_mdct(d_in, d_out, d_window, N, streams, frames, hop, stream_stride);
-    if (chk != 0) return chk < 0 ? -1 : 0;
-    return timed_launch(FFT_time, [&] { return dispatch_mdct(d_in, d_out, d_window, N, streams, frames, hop, stream_stride, 0, nullptr); });
+    return checked_benchmark(check_mdct(d_in, d_out, d_window, N, streams, frames, hop, stream_stride),
+                             dispatch_mdct(d_in, d_out, d_window, N, streams, frames, hop, stream_stride), FFT_time);
 }
 
 int smfft_imdct_launch(const void* d_in, void* d_out, const void* d_window, int N, long long batch, void* hip_stream) {
-    const int chk = check_imdct(d_in, d_out, d_window, N, batch);
-    if (chk != 0) return chk < 0 ? -1 : 0;
-    return dispatch_imdct(d_in, d_out, d_window, N, batch, 0, (hipStream_t)hip_stream);
+    return checked_launch(check_imdct(d_in, d_out, d_window, N, batch), dispatch_imdct(d_in, d_out, d_window, N, batch), hip_stream);
 }
 
 int smfft_imdct_launch_tuned(const void* d_in, void* d_out, const void* d_window, int N, long long batch, void* hip_stream, int grid) {
-    const int chk = check_imdct(d_in, d_out, d_window, N, batch);
-    if (chk < 0 || grid < 1) return -1;
-    if (chk != 0) return 0;
-    return dispatch_imdct(d_in, d_out, d_window, N, batch, grid, (hipStream_t)hip_stream);
+    return checked_launch_tuned(check_imdct(d_in, d_out, d_window, N, batch), dispatch_imdct(d_in, d_out, d_window, N, batch), hip_stream, grid);
 }
 
 int smfft_imdct_benchmark(const void* d_in, void* d_out, const void* d_window, int N, long long batch, double* FFT_time) {
-    const int chk = check_imdct(d_in, d_out, d_window, N, batch);
-    if (chk != 0) return chk < 0 ? -1 : 0;
-    return timed_launch(FFT_time, [&] { return dispatch_imdct(d_in, d_out, d_window, N, batch, 0, nullptr); });
+    return checked_benchmark(check_imdct(d_in, d_out, d_window, N, batch), dispatch_imdct(d_in, d_out, d_window, N, batch), FFT_time);
 }
 
 }  // extern "C"

@@ -260,10 +260,9 @@ int launch_rows<SMFFT_ROWCONV_REAL_N>(const float* a, const float* b, float* out
 }  // namespace smfft
 
 #else  // the C ABI
-#include "smfft_addon_host.hpp"
+#include "smfft_rows_host.hpp"
 
 namespace {
-constexpr int kGridCap = 12288;     // smfft_fir_kernel.hpp kFirGridCap: workgroups along the tiles, grid-strided beyond
 constexpr int kMaxFull = 4096;      // the largest n_a + n_b - 1
 
 // M: the smallest of 256 ... 4096 with M >= n_a + n_b - 1; -1 outside the range (the sum is taken in 64 bits: no overflow at INT_MAX)
@@ -274,24 +273,15 @@ int fft_size(int n_a, int n_b) {
     return M;
 }
 
-// grid <= 0: the default, min(tiles, kGridCap)
-int dispatch(const void* a, const void* b, void* out, int n_a, int n_b, int first, int m, long long batch, int correlate, int grid, hipStream_t stream) {
-    const int M = fft_size(n_a, n_b);
-    if (grid <= 0) {
-        const long long tiles = (batch + 4096 / M - 1) / (4096 / M);
-        grid = (int)(tiles < kGridCap ? tiles : kGridCap);
-    }
-    const float *x = (const float*)a, *h = (const float*)b;
-    float* y = (float*)out;
-    correlate = correlate != 0;
-    switch (M) {
-        case 256: return smfft::rowconv_real::launch_rows<256>(x, h, y, n_a, n_b, first, m, batch, correlate, grid, stream);
-        case 512: return smfft::rowconv_real::launch_rows<512>(x, h, y, n_a, n_b, first, m, batch, correlate, grid, stream);
-        case 1024: return smfft::rowconv_real::launch_rows<1024>(x, h, y, n_a, n_b, first, m, batch, correlate, grid, stream);
-        case 2048: return smfft::rowconv_real::launch_rows<2048>(x, h, y, n_a, n_b, first, m, batch, correlate, grid, stream);
-        case 4096: return smfft::rowconv_real::launch_rows<4096>(x, h, y, n_a, n_b, first, m, batch, correlate, grid, stream);
-    }
-    return -1;
+// the launch of `grid` workgroups (<= 0: the default) on `stream`
+auto dispatch(const void* a, const void* b, void* out, int n_a, int n_b, int first, int m, long long batch, int correlate) {
+    return [=](int grid, hipStream_t stream) {
+        const int M = fft_size(n_a, n_b);
+        grid = default_grid(M, batch, grid);
+        return dispatch_m(M, [&](auto len) {
+            return smfft::rowconv_real::launch_rows<len()>((const float*)a, (const float*)b, (float*)out, n_a, n_b, first, m, batch, correlate != 0, grid, stream);
+        });
+    };
 }
 
 // -1: refused; 0: launch; 1: nothing to do.  No HIP call.  The window lies inside the full result (first + m in 64 bits); the output is
@@ -308,23 +298,16 @@ extern "C" {
 int smfft_rowconv_real_fft_size(int n_a, int n_b) { return fft_size(n_a, n_b); }
 
 int smfft_rowconv_real_launch(const void* d_a, const void* d_b, void* d_out, int n_a, int n_b, int first, int m, long long batch, int correlate, void* hip_stream) {
-    const int chk = check(d_a, d_b, d_out, n_a, n_b, first, m, batch);
-    if (chk != 0) return chk < 0 ? -1 : 0;
-    return dispatch(d_a, d_b, d_out, n_a, n_b, first, m, batch, correlate, 0, (hipStream_t)hip_stream);
+    return checked_launch(check(d_a, d_b, d_out, n_a, n_b, first, m, batch), dispatch(d_a, d_b, d_out, n_a, n_b, first, m, batch, correlate), hip_stream);
 }
 
 int smfft_rowconv_real_launch_tuned(const void* d_a, const void* d_b, void* d_out, int n_a, int n_b, int first, int m, long long batch, int correlate, void* hip_stream,
                                     int grid) {
-    const int chk = check(d_a, d_b, d_out, n_a, n_b, first, m, batch);
-    if (chk < 0 || grid < 1) return -1;
-    if (chk != 0) return 0;
-    return dispatch(d_a, d_b, d_out, n_a, n_b, first, m, batch, correlate, grid, (hipStream_t)hip_stream);
+    return checked_launch_tuned(check(d_a, d_b, d_out, n_a, n_b, first, m, batch), dispatch(d_a, d_b, d_out, n_a, n_b, first, m, batch, correlate), hip_stream, grid);
 }
 
 int smfft_rowconv_real_benchmark(const void* d_a, const void* d_b, void* d_out, int n_a, int n_b, int first, int m, long long batch, int correlate, double* FFT_time) {
-    const int chk = check(d_a, d_b, d_out, n_a, n_b, first, m, batch);
-    if (chk != 0) return chk < 0 ? -1 : 0;
-    return timed_launch(FFT_time, [&] { return dispatch(d_a, d_b, d_out, n_a, n_b, first, m, batch, correlate, 0, nullptr); });
+    return checked_benchmark(check(d_a, d_b, d_out, n_a, n_b, first, m, batch), dispatch(d_a, d_b, d_out, n_a, n_b, first, m, batch, correlate), FFT_time);
 }
 
 }  // extern "C"

@@ -24,8 +24,8 @@
 //     y[2p] = w[2p] Re z[p] / n, y[2p+1] = w[2p+1] Im z[p] / n: one 8-byte store per element.  1 / n is a power of two: exact.
 //
 // Twiddles: W_n^k (k < M) is the row that the DCT kernels build at compile time from the fp64-rounded first octant of W_32768
-// (smfft_twiddles_dct.inc) by exact symmetries, built here once more from the same table so that the other libraries and their kernels
-// stay as they are.  No v_sin / v_cos.
+// (smfft_twiddles_dct.inc) by exact symmetries (smfft_rows.hpp), in an object of this library's own so that the other libraries and
+// their kernels stay as they are.  No v_sin / v_cos.
 //
 // Cache policy, by measurement (tools/ab_stft.py, profiles/r25_stft_ab.txt): the sample loads of the forward
 // kernels are plain -- overlapping frames fetch a sample from HBM once and from L2 after that, and at hop = n / 4 the launch with
@@ -54,6 +54,7 @@ int launch_istft(const float2* in, float* out, const float* window, long long ba
 
 #ifdef SMFFT_STFT_N
 #include "smfft_fir_kernel.hpp"
+#include "smfft_rows.hpp"
 
 // the policy of the sample loads (forward), of the loads of the bins (inverse) and of the stores: 1 non-temporal, 0 plain
 #ifndef SMFFT_STFT_NT_LOAD
@@ -69,16 +70,7 @@ int launch_istft(const float2* in, float* out, const float* window, long long ba
 namespace smfft {
 namespace stft {
 
-static constexpr TwiddleValue octant_32768[4097] = {
-#include "smfft/smfft_twiddles_dct.inc"
-};
-
-// (cos, sin)(2 pi m / 32768), 0 <= m < 16384, from the octant: exact symmetries, so every entry is an fp64 value rounded once
-constexpr TwiddleValue w32768(int m) {
-    const int q = m / 4096, r = m % 4096;
-    const TwiddleValue a = octant_32768[r], b = octant_32768[4096 - r];
-    return q == 0 ? TwiddleValue{a.x, a.y} : q == 1 ? TwiddleValue{b.y, b.x} : q == 2 ? TwiddleValue{-a.y, a.x} : TwiddleValue{-b.x, b.y};
-}
+using rows::w32768, rows::row_entry, rows::per_tile;
 
 // the twiddle row of n = 2 M points as (cos, sin)(2 pi k / n), that is the CONJUGATE of W_n^k
 template <int M>
@@ -91,64 +83,14 @@ struct Rows {
 template <int M>
 static __device__ const Rows<M> rows = Rows<M>();
 
-__device__ __forceinline__ float2 row_entry(const TwiddleValue* p) {
-    const TwiddleValue v = *p;
-    return make_float2(v.x, v.y);
-}
-
-// v, as a value the compiler takes for new in every tile: the twiddle loads indexed with it stay inside the tile loop (smfft_dct.hip)
-__device__ __forceinline__ int per_tile(int v) {
-    asm volatile("" : "+v"(v));
-    return v;
-}
-
 // two consecutive floats at 4-byte alignment (samples, window) and one complex value at 8-byte alignment, with the policies above
-typedef float row_pair __attribute__((ext_vector_type(2), aligned(4)));
-typedef float bin_pair __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ float2 gload2(const float* p) {
-#if SMFFT_STFT_NT_LOAD
-    const row_pair v = __builtin_nontemporal_load(reinterpret_cast<const row_pair*>(p));
-#else
-    const row_pair v = *reinterpret_cast<const row_pair*>(p);
-#endif
-    return make_float2(v.x, v.y);
-}
-__device__ __forceinline__ float2 gloadc(const float2* p) {
-#if SMFFT_STFT_NT_BINS
-    const bin_pair v = __builtin_nontemporal_load(reinterpret_cast<const bin_pair*>(p));
-#else
-    const bin_pair v = *reinterpret_cast<const bin_pair*>(p);
-#endif
-    return make_float2(v.x, v.y);
-}
+__device__ __forceinline__ float2 gload2(const float* p) { return rows::gload2<SMFFT_STFT_NT_LOAD != 0>(p); }
+__device__ __forceinline__ float2 gloadc(const float2* p) { return rows::gloadc<SMFFT_STFT_NT_BINS != 0>(p); }
 // the window: plain loads, every frame reads it
-__device__ __forceinline__ float2 wload2(const float* p) {
-    const row_pair v = *reinterpret_cast<const row_pair*>(p);
-    return make_float2(v.x, v.y);
-}
-__device__ __forceinline__ void gstore1(float* p, float v) {
-#if SMFFT_STFT_NT_STORE
-    __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
-}
-__device__ __forceinline__ void gstore2(float* p, float a, float b) {
-    const row_pair v = {a, b};
-#if SMFFT_STFT_NT_STORE
-    __builtin_nontemporal_store(v, reinterpret_cast<row_pair*>(p));
-#else
-    *reinterpret_cast<row_pair*>(p) = v;
-#endif
-}
-__device__ __forceinline__ void gstorec(float2* p, float a, float b) {
-    const bin_pair v = {a, b};
-#if SMFFT_STFT_NT_STORE
-    __builtin_nontemporal_store(v, reinterpret_cast<bin_pair*>(p));
-#else
-    *reinterpret_cast<bin_pair*>(p) = v;
-#endif
-}
+__device__ __forceinline__ float2 wload2(const float* p) { return rows::gload2<false>(p); }
+__device__ __forceinline__ void gstore1(float* p, float v) { rows::gstore1<SMFFT_STFT_NT_STORE != 0>(p, v); }
+__device__ __forceinline__ void gstore2(float* p, float a, float b) { rows::gstore2<SMFFT_STFT_NT_STORE != 0>(p, a, b); }
+__device__ __forceinline__ void gstorec(float2* p, float a, float b) { rows::gstorec<SMFFT_STFT_NT_STORE != 0>(p, a, b); }
 
 // frame g = c frames + f < total reads in[c stream_stride + f hop ... + n), n = 2 M, under window[0, n) (null: all ones).
 // KIND 0: out[2 (g (M + 1) + k)], out[2 (g (M + 1) + k) + 1] = Re, Im X[k]; KIND 1: out[g (M + 1) + k] = |X[k]|^2; k <= M
@@ -316,66 +258,37 @@ int launch_istft<SMFFT_STFT_N>(const float2* in, float* out, const float* window
 }  // namespace smfft
 
 #else  // the C ABI
-#include <cstdint>
-
-#include "smfft_addon_host.hpp"
+#include "smfft_rows_host.hpp"
 
 namespace {
-constexpr int kGridCap = 12288;     // smfft_fir_kernel.hpp kFirGridCap: workgroups along the tiles, grid-strided beyond
 constexpr unsigned long long kMaxElements = 1ull << 59;      // floats of a buffer: keeps the byte counts below inside 64 bits
 
-// M = n / 2 for n a power of two in 512 ... 8192; -1 otherwise
-int fft_size(int n) {
-    if (n < 512 || n > 8192 || (n & (n - 1)) != 0) return -1;
-    return n / 2;
+// the launches of `grid` workgroups (<= 0: the default) on `stream`
+auto dispatch_stft(const void* in, void* out, const void* window, int n, long long streams, long long frames, long long hop, long long stream_stride,
+                   int kind) {
+    return [=](int grid, hipStream_t stream) {
+        const int M = half_length_fft_size(n);
+        const long long total = streams * frames;
+        grid = default_grid(M, total, grid);
+        return dispatch_m(M, [&](auto m) {
+            return smfft::stft::launch_stft<m()>((const float*)in, (float*)out, (const float*)window, total, frames, hop, stream_stride, kind, grid, stream);
+        });
+    };
 }
 
-// grid <= 0: the default, min(tiles, kGridCap)
-int default_grid(int M, long long rows, int grid) {
-    if (grid > 0) return grid;
-    const long long tiles = (rows + 4096 / M - 1) / (4096 / M);
-    return (int)(tiles < kGridCap ? tiles : kGridCap);
-}
-
-// do [a, a + na floats) and [b, b + nb floats) share a byte
-bool overlap(const void* a, unsigned long long na, const void* b, unsigned long long nb) {
-    const std::uintptr_t pa = (std::uintptr_t)a, pb = (std::uintptr_t)b;
-    return pa < pb ? pb - pa < na * sizeof(float) : pa - pb < nb * sizeof(float);
-}
-
-#define SMFFT_STFT_DISPATCH(M, call)                    \
-    switch (M) {                                        \
-        case 256: return smfft::stft::call(256);        \
-        case 512: return smfft::stft::call(512);        \
-        case 1024: return smfft::stft::call(1024);      \
-        case 2048: return smfft::stft::call(2048);      \
-        case 4096: return smfft::stft::call(4096);      \
-    }                                                   \
-    return -1
-
-int dispatch_stft(const void* in, void* out, const void* window, int n, long long streams, long long frames, long long hop, long long stream_stride,
-                  int kind, int grid, hipStream_t stream) {
-    const int M = fft_size(n);
-    const long long total = streams * frames;
-    grid = default_grid(M, total, grid);
-#define SMFFT_STFT_CALL(m) launch_stft<m>((const float*)in, (float*)out, (const float*)window, total, frames, hop, stream_stride, kind, grid, stream)
-    SMFFT_STFT_DISPATCH(M, SMFFT_STFT_CALL);
-#undef SMFFT_STFT_CALL
-}
-
-int dispatch_istft(const void* in, void* out, const void* window, int n, long long batch, int grid, hipStream_t stream) {
-    const int M = fft_size(n);
-    grid = default_grid(M, batch, grid);
-#define SMFFT_STFT_CALL(m) launch_istft<m>((const float2*)in, (float*)out, (const float*)window, batch, grid, stream)
-    SMFFT_STFT_DISPATCH(M, SMFFT_STFT_CALL);
-#undef SMFFT_STFT_CALL
+auto dispatch_istft(const void* in, void* out, const void* window, int n, long long batch) {
+    return [=](int grid, hipStream_t stream) {
+        const int M = half_length_fft_size(n);
+        grid = default_grid(M, batch, grid);
+        return dispatch_m(M, [&](auto m) { return smfft::stft::launch_istft<m()>((const float2*)in, (float*)out, (const float*)window, batch, grid, stream); });
+    };
 }
 
 // -1: refused; 0: launch; 1: nothing to do.  No HIP call.
 // stft: the output overlaps neither the range of the frames nor the window
 int check_stft(const void* in, const void* out, const void* window, int n, long long streams, long long frames, long long hop, long long stream_stride,
                int kind) {
-    const int M = fft_size(n);
+    const int M = half_length_fft_size(n);
     if (M < 0 || kind < 0 || kind > 1 || streams < 0 || frames < 0 || hop < 1 || stream_stride < 1) return -1;
     if (streams == 0 || frames == 0) return 1;
     const unsigned __int128 total = (unsigned __int128)streams * (unsigned __int128)frames;
@@ -391,7 +304,7 @@ int check_stft(const void* in, const void* out, const void* window, int n, long 
 
 // istft: the output overlaps neither the input nor the window
 int check_istft(const void* in, const void* out, const void* window, int n, long long batch) {
-    const int M = fft_size(n);
+    const int M = half_length_fft_size(n);
     if (M < 0 || batch < 0) return -1;
     if (batch == 0) return 1;
     if ((unsigned long long)batch > kMaxElements / (2u * (unsigned)n)) return -1;
@@ -404,49 +317,38 @@ int check_istft(const void* in, const void* out, const void* window, int n, long
 
 extern "C" {
 
-int smfft_stft_fft_size(int n) { return fft_size(n); }
+int smfft_stft_fft_size(int n) { return half_length_fft_size(n); }
 
 long long smfft_stft_frames(long long L, int n, long long hop) {
-    if (fft_size(n) < 0 || hop < 1 || L < 0) return -1;
+    if (half_length_fft_size(n) < 0 || hop < 1 || L < 0) return -1;
     return L < n ? 0 : 1 + (L - n) / hop;
 }
 
 int smfft_stft_launch(const void* d_in, void* d_out, const void* d_window, int n, long long streams, long long frames, long long hop, long long stream_stride, int kind, void* hip_stream) {
-    const int chk = check_stft(d_in, d_out, d_window, n, streams, frames, hop, stream_stride, kind);
-    if (chk != 0) return chk < 0 ? -1 : 0;
-    return dispatch_stft(d_in, d_out, d_window, n, streams, frames, hop, stream_stride, kind, 0, (hipStream_t)hip_stream);
+    return checked_launch(check_stft(d_in, d_out, d_window, n, streams, frames, hop, stream_stride, kind),
+                          dispatch_stft(d_in, d_out, d_window, n, streams, frames, hop, stream_stride, kind), hip_stream);
 }
 
 int smfft_stft_launch_tuned(const void* d_in, void* d_out, const void* d_window, int n, long long streams, long long frames, long long hop, long long stream_stride, int kind, void* hip_stream, int grid) {
-    const int chk = check_stft(d_in, d_out, d_window, n, streams, frames, hop, stream_stride, kind);
-    if (chk < 0 || grid < 1) return -1;
-    if (chk != 0) return 0;
-    return dispatch_stft(d_in, d_out, d_window, n, streams, frames, hop, stream_stride, kind, grid, (hipStream_t)hip_stream);
+    return checked_launch_tuned(check_stft(d_in, d_out, d_window, n, streams, frames, hop, stream_stride, kind),
+                                dispatch_stft(d_in, d_out, d_window, n, streams, frames, hop, stream_stride, kind), hip_stream, grid);
 }
 
 int smfft_stft_benchmark(const void* d_in, void* d_out, const void* d_window, int n, long long streams, long long frames, long long hop, long long stream_stride, int kind, double* FFT_time) {
-    const int chk = check_stft(d_in, d_out, d_window, n, streams, frames, hop, stream_stride, kind);
-    if (chk != 0) return chk < 0 ? -1 : 0;
-    return timed_launch(FFT_time, [&] { return dispatch_stft(d_in, d_out, d_window, n, streams, frames, hop, stream_stride, kind, 0, nullptr); });
+    return checked_benchmark(check_stft(d_in, d_out, d_window, n, streams, frames, hop, stream_stride, kind),
+                             dispatch_stft(d_in, d_out, d_window, n, streams, frames, hop, stream_stride, kind), FFT_time);
 }
 
 int smfft_istft_launch(const void* d_in, void* d_out, const void* d_window, int n, long long batch, void* hip_stream) {
-    const int chk = check_istft(d_in, d_out, d_window, n, batch);
-    if (chk != 0) return chk < 0 ? -1 : 0;
-    return dispatch_istft(d_in, d_out, d_window, n, batch, 0, (hipStream_t)hip_stream);
+    return checked_launch(check_istft(d_in, d_out, d_window, n, batch), dispatch_istft(d_in, d_out, d_window, n, batch), hip_stream);
 }
 
 int smfft_istft_launch_tuned(const void* d_in, void* d_out, const void* d_window, int n, long long batch, void* hip_stream, int grid) {
-    const int chk = check_istft(d_in, d_out, d_window, n, batch);
-    if (chk < 0 || grid < 1) return -1;
-    if (chk != 0) return 0;
-    return dispatch_istft(d_in, d_out, d_window, n, batch, grid, (hipStream_t)hip_stream);
+    return checked_launch_tuned(check_istft(d_in, d_out, d_window, n, batch), dispatch_istft(d_in, d_out, d_window, n, batch), hip_stream, grid);
 }
 
 int smfft_istft_benchmark(const void* d_in, void* d_out, const void* d_window, int n, long long batch, double* FFT_time) {
-    const int chk = check_istft(d_in, d_out, d_window, n, batch);
-    if (chk != 0) return chk < 0 ? -1 : 0;
-    return timed_launch(FFT_time, [&] { return dispatch_istft(d_in, d_out, d_window, n, batch, 0, nullptr); });
+    return checked_benchmark(check_istft(d_in, d_out, d_window, n, batch), dispatch_istft(d_in, d_out, d_window, n, batch), FFT_time);
 }
 
 }  // extern "C"

@@ -17,6 +17,8 @@ import ctypes
 import numpy as np
 
 from . import _addon
+from ._rows import check_tensor as _check_tensor
+from ._rows import host_round_trip as _host_round_trip
 
 SIZES = (256, 512, 1024, 2048, 4096)          # the inner transform lengths M = n / 2
 LENGTHS = (512, 1024, 2048, 4096, 8192)       # the row lengths n
@@ -73,17 +75,6 @@ def benchmark(d_in, d_out, n, batch, type=2, sine=False):
     return rc, t.value
 
 
-def _check_tensor(x, what):
-    import torch
-    if not isinstance(x, torch.Tensor):
-        raise TypeError(f"{what} must be a torch tensor on the device, not {type(x).__name__}")
-    if x.dtype != torch.float32:
-        raise TypeError(f"{what} must be float32, not {x.dtype}")
-    if x.ndim < 1 or not x.is_contiguous():
-        raise ValueError(f"{what} must be contiguous with at least one axis")
-    return x
-
-
 def launch(x, out=None, type=2, sine=False, stream=None):
     """x: a contiguous float32 torch tensor on the device, rows on the last axis; out: such a tensor of the same shape, x itself (in
     place), or None for a new one.  Enqueues one launch on `stream` (a hipStream_t as an integer; None = torch's current stream of x's
@@ -124,18 +115,8 @@ def _transform(x, type, sine):
     x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1, n)
     batch = x.shape[0]
     handle = lib()
-    from . import api      # the device allocator and the copies of libsmfft_amd.so
-    din, dout = api.DeviceBuffer.from_host(x), api.DeviceBuffer(max(batch * n * 4, 4))
-    api.lib.smfft_memset(dout.ptr, 0xFF, dout.nbytes)   # NaN pattern: untouched outputs are caught
-    rc = handle.smfft_dct_launch(din.ptr, dout.ptr, n, batch, type, int(bool(sine)), None)
-    if rc == 0:
-        rc = api.lib.smfft_synchronize()
-    if rc != 0:
-        raise RuntimeError(f"dct(n={n}, batch={batch}, type={type}, sine={bool(sine)}) -> {rc}")
-    out = dout.to_host(np.float32, (batch, n)).reshape(shape)
-    for buf in (din, dout):
-        buf.free()
-    return out
+    return _host_round_trip(x, np.float32, lambda din, dout: handle.smfft_dct_launch(din, dout, n, batch, type, int(bool(sine)), None),
+                            f"dct(n={n}, batch={batch}, type={type}, sine={bool(sine)})").reshape(shape)
 
 
 def dct(x, type=2):

@@ -17,6 +17,8 @@ import ctypes
 import numpy as np
 
 from . import _addon
+from ._rows import check_tensor as _check_tensor
+from ._rows import host_round_trip as _host_round_trip
 
 SIZES = (256, 512, 1024, 2048, 4096)          # the inner transform lengths M = n / 2
 LENGTHS = (512, 1024, 2048, 4096, 8192)       # the row lengths n
@@ -73,17 +75,6 @@ def benchmark(d_in, d_out, n, batch, kind=QUADRATURE):
     return rc, t.value
 
 
-def _check_tensor(x, what, dtype):
-    import torch
-    if not isinstance(x, torch.Tensor):
-        raise TypeError(f"{what} must be a torch tensor on the device, not {type(x).__name__}")
-    if x.dtype != dtype:
-        raise TypeError(f"{what} must be {dtype}, not {x.dtype}")
-    if x.ndim < 1 or not x.is_contiguous():
-        raise ValueError(f"{what} must be contiguous with at least one axis")
-    return x
-
-
 def launch(x, out=None, kind=QUADRATURE, stream=None):
     """x: a contiguous float32 torch tensor on the device, rows on the last axis; out: a contiguous tensor of the same shape -- float32,
     or complex64 for the analytic kind --, x itself (in place: kinds 0 and 2), or None for a new one.  Enqueues one launch on `stream`
@@ -125,20 +116,9 @@ def _transform(x, kind):
     shape = x.shape
     x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1, n)
     batch = x.shape[0]
-    out_dtype, size = (np.complex64, 8) if kind == ANALYTIC else (np.float32, 4)
     handle = lib()
-    from . import api      # the device allocator and the copies of libsmfft_amd.so
-    din, dout = api.DeviceBuffer.from_host(x), api.DeviceBuffer(max(batch * n * size, size))
-    api.lib.smfft_memset(dout.ptr, 0xFF, dout.nbytes)   # NaN pattern: untouched outputs are caught
-    rc = handle.smfft_hilbert_launch(din.ptr, dout.ptr, n, batch, kind, None)
-    if rc == 0:
-        rc = api.lib.smfft_synchronize()
-    if rc != 0:
-        raise RuntimeError(f"hilbert(n={n}, batch={batch}, kind={kind}) -> {rc}")
-    out = dout.to_host(out_dtype, (batch, n)).reshape(shape)
-    for buf in (din, dout):
-        buf.free()
-    return out
+    return _host_round_trip(x, np.complex64 if kind == ANALYTIC else np.float32, lambda din, dout: handle.smfft_hilbert_launch(din, dout, n, batch, kind, None),
+                            f"hilbert(n={n}, batch={batch}, kind={kind})").reshape(shape)
 
 
 def hilbert(x):

@@ -21,6 +21,8 @@ import ctypes
 import numpy as np
 
 from . import _addon
+from ._rows import check_tensor as _check_tensor
+from ._rows import host_round_trip as _host_round_trip
 
 SIZES = (256, 512, 1024, 2048, 4096)          # the inner transform lengths M = n / 2
 LENGTHS = (512, 1024, 2048, 4096, 8192)       # the row lengths n, and the coefficients per frame N
@@ -117,17 +119,6 @@ def imdct_benchmark(d_in, d_out, d_window, N, batch):
 
 
 # ---- tensors ---------------------------------------------------------------------------------------------------------------------------
-def _check_tensor(x, what, axes=1):
-    import torch
-    if not isinstance(x, torch.Tensor):
-        raise TypeError(f"{what} must be a torch tensor on the device, not {type(x).__name__}")
-    if x.dtype != torch.float32:
-        raise TypeError(f"{what} must be float32, not {x.dtype}")
-    if x.ndim < axes or not x.is_contiguous():
-        raise ValueError(f"{what} must be contiguous with at least {axes} axis" + ("" if axes == 1 else " (axes)"))
-    return x
-
-
 def _check_window(window, N, x):
     if window is None:
         return None
@@ -185,17 +176,8 @@ def _transform(x, sine):
     x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1, n)
     batch = x.shape[0]
     handle = lib()
-    from . import api      # the device allocator and the copies of libsmfft_amd.so
-    din, dout = api.DeviceBuffer.from_host(x), api.DeviceBuffer(max(batch * n * 4, 4))
-    api.lib.smfft_memset(dout.ptr, 0xFF, dout.nbytes)   # NaN pattern: untouched outputs are caught
-    rc = handle.smfft_dct4_launch(din.ptr, dout.ptr, n, batch, int(bool(sine)), None)
-    if rc == 0:
-        rc = api.lib.smfft_synchronize()
-    _raise(rc, f"dct4(n={n}, batch={batch}, sine={bool(sine)})")
-    out = dout.to_host(np.float32, (batch, n)).reshape(shape)
-    for buf in (din, dout):
-        buf.free()
-    return out
+    return _host_round_trip(x, np.float32, lambda din, dout: handle.smfft_dct4_launch(din, dout, n, batch, int(bool(sine)), None),
+                            f"dct4(n={n}, batch={batch}, sine={bool(sine)})").reshape(shape)
 
 
 def dct4(x):
@@ -232,7 +214,7 @@ def mdct(x, window=None, stream=None):
 def mdct_frames(signal, window, N, stream=None):
     """the lapped transform: signal (C, L) float32 on the device, L a multiple of N and at least 2N -> (C, L / N - 1, N), frame f of
     stream c from signal[c, f N ... f N + 2N), in one launch that reads every sample from the signal itself"""
-    s = _check_tensor(signal, "signal", 2)
+    s = _check_tensor(signal, "signal", axes=2)
     N = _check(N)
     if s.ndim != 2 or s.shape[1] % N or s.shape[1] < 2 * N:
         raise ValueError(f"signal must be (C, L) with L a multiple of N = {N} and at least 2N, not {tuple(s.shape)}")

@@ -19,6 +19,7 @@ import ctypes
 import numpy as np
 
 from . import _addon
+from ._rows import check_tensor as _check_tensor
 
 SIZES = (256, 512, 1024, 2048, 4096)          # the inner transform lengths M = n / 2
 LENGTHS = (512, 1024, 2048, 4096, 8192)       # the frame lengths n
@@ -103,18 +104,6 @@ def istft_benchmark(d_in, d_out, d_window, n, batch):
 
 
 # ---- tensors ---------------------------------------------------------------------------------------------------------------------------
-def _check_tensor(x, what, dtype=None, axes=1):
-    import torch
-    dtype = torch.float32 if dtype is None else dtype
-    if not isinstance(x, torch.Tensor):
-        raise TypeError(f"{what} must be a torch tensor on the device, not {type(x).__name__}")
-    if x.dtype != dtype:
-        raise TypeError(f"{what} must be {dtype}, not {x.dtype}")
-    if x.ndim < axes or not x.is_contiguous():
-        raise ValueError(f"{what} must be contiguous with at least {axes} ax" + ("is" if axes == 1 else "es"))
-    return x
-
-
 def _check_window(window, n, x):
     if window is None:
         return None

@@ -1,7 +1,9 @@
 """What the CPU tests of the add-on libraries share (test_large_cpu.py, test_large_real_cpu.py, test_large_fir_cpu.py, test_pfb_cpu.py,
-test_pfb_real_cpu.py, test_fir_real_cpu.py; the FIR checks at the end serve test_fir_cpu.py, the main library's bank, too):
-the per-length flags of the Makefile, the compile of a per-length object to gfx950 assembly as the Makefile compiles it, the fields of
-a kernel descriptor, the declarations of a C header as ctypes signatures, and the walk through a kernel inventory."""
+test_pfb_real_cpu.py, test_fir_real_cpu.py, the eight test_sm_*_cpu.py of the row libraries; the FIR checks at the end serve
+test_fir_cpu.py, the main library's bank, too): the per-length flags of the Makefile, the compile of a per-length object -- or of all
+of a library's -- to gfx950 assembly as the Makefile compiles it, the fields of a kernel descriptor, the occupancy a register count
+allows, the declarations of a C header as ctypes signatures, the exported symbols, the walk through a kernel inventory, and what every
+mirror's import and the no-device subprocesses are held to."""
 import ctypes
 import os
 import re
@@ -44,6 +46,59 @@ def descriptor_field(descs, name, field):
     m = re.search(rf"\.amdhsa_{field} (\d+)", descs[name])
     assert m, (name, field)
     return int(m.group(1))
+
+
+def occupancy(vgprs):
+    """waves per SIMD that the vector registers allow: 512 registers in granules of 8"""
+    return 512 // (-(-vgprs // 8) * 8)
+
+
+def addon_isa(stem, prefix, sizes, tmp, extra=()):
+    """{N: gfx950 assembly of <stem>_<N>.o as the Makefile compiles it: -I. and <prefix>_FLAGS_<N>, then `extra`}"""
+    import concurrent.futures
+
+    def compile_one(n):
+        flags = ["-I" + CSRC] + makefile_flags(prefix, n) + [f"-DSMFFT_{prefix}_N={n}"] + list(extra)
+        return device_asm(os.path.join(CSRC, stem + ".hip"), flags, tmp / f"{stem}_{n}.s")
+    with concurrent.futures.ThreadPoolExecutor(len(sizes)) as pool:
+        return dict(zip(sizes, pool.map(compile_one, sizes)))
+
+
+def check_exports(lib_path, names):
+    """the library's defined dynamic symbols named smfft_* are exactly `names`"""
+    nm = subprocess.run(["nm", "-D", "--defined-only", lib_path], capture_output=True, text=True, check=True).stdout
+    assert sorted(re.findall(r" T (smfft_\w+)$", nm, re.M)) == sorted(names)
+
+
+def check_isa_identity_lists(stem, prefix, sizes):
+    """tools/isa_identity.py compiles the library's per-length objects with the Makefile's flags and -I., like the other add-ons' (the
+    tool itself needs the history of a git checkout and minutes of compiling: it is run by hand)"""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import isa_identity
+    assert (stem, prefix, sizes, True) in isa_identity.ADDONS
+    names = [u[0] for u in isa_identity.units(ROOT)]
+    assert all(f"{stem}_{n}" in names for n in sizes) and len(names) == len(set(names))
+
+
+def check_import_does_not_load(module, lib_stem):
+    """importing smfft_amd.<module> maps no lib<lib_stem>: the mirror loads its library on first use"""
+    import sys
+    code = (f"import sys; sys.path.insert(0, sys.argv[1]); import smfft_amd, smfft_amd.{module} as l; assert l._lib is None; "
+            f"maps = open('/proc/self/maps').read(); assert 'lib{lib_stem}' not in maps; print('ok')")
+    p = subprocess.run([sys.executable, "-c", code, ROOT], capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0 and "ok" in p.stdout, p.stdout + p.stderr
+
+
+# pasted in front of the scripts of the no-device subprocesses: f(*a, **k) raises exc, or the script ends with a message
+REFUSED = '''
+def refused(exc, f, *a, **k):
+    try:
+        f(*a, **k)
+    except exc:
+        return
+    raise SystemExit(f"{f.__name__}{a}{k} was not refused with {exc.__name__}")
+'''
 
 
 def declarations(header):
@@ -89,16 +144,6 @@ PFB_KERNEL_HEADER = os.path.join(CSRC, "smfft_pfb_kernel.hpp")      # the one ke
 PFB_WORKGROUPS_PER_CU = 3
 PFB_VGPR_BUDGET = 168          # three waves per SIMD: 512 registers / 3, in granules of 8; the persistent grid rests on it
 LDS_PER_CU = 160 * 1024
-
-
-def pfb_isa(stem, prefix, tmp):
-    """{N: gfx950 assembly of <stem>_<N>.o as the Makefile compiles it: -I. and <prefix>_FLAGS_<N>}"""
-    import concurrent.futures
-
-    def compile_one(n):
-        return device_asm(os.path.join(CSRC, stem + ".hip"), ["-I" + CSRC] + makefile_flags(prefix, n) + [f"-DSMFFT_{prefix}_N={n}"], tmp / f"{stem}_{n}.s")
-    with concurrent.futures.ThreadPoolExecutor(len(PFB_SIZES)) as pool:
-        return dict(zip(PFB_SIZES, pool.map(compile_one, PFB_SIZES)))
 
 
 def pfb_kernels(text, kernel):

@@ -89,11 +89,6 @@ def _bodies(text, frag):
     return found
 
 
-def _occupancy(vgprs):
-    """waves per SIMD that the vector registers allow: 512 registers in granules of 8"""
-    return 512 // (-(-vgprs // 8) * 8)
-
-
 @pytest.fixture(scope="module")
 def isa(tmp_path_factory):
     """{N: assembly of smfft_fir_detect_<N>.o as the Makefile compiles it}, and the assembly of the main library's smfft_fir.hip"""
@@ -146,7 +141,7 @@ def test_isa_budget_of_what_ships(isa):
         assert not re.search(r"\bscratch_", text), n
         cname = next(k for k in cdescs if "fir_overlap_save_kernelILi%dE" % n in k)
         vc = ac.descriptor_field(cdescs, cname, "next_free_vgpr")
-        assert _occupancy(vc) == 2, (n, vc)
+        assert ac.occupancy(vc) == 2, (n, vc)
         for kind, (name, body) in (("power", next(iter(power.items()))), ("peak", next(iter(peak.items())))):
             assert "ILi%dE" % n in name
             assert not [line for line in body if line.startswith("scratch_")], name
@@ -172,7 +167,7 @@ def test_isa_budget_of_what_ships(isa):
                 assert len(stores) == 32 and {depth[i] for i in stores} == {1}, (name, len(stores))      # once per segment, behind the filter loop
             v = ac.descriptor_field(descs, name, "next_free_vgpr")
             print(f"N={n}: fir_{kind}_kernel {v} VGPRs (complex bank: {vc}), {lds} B of LDS")
-            assert v <= 256 and _occupancy(v) >= _occupancy(vc), (name, v, vc)
+            assert v <= 256 and ac.occupancy(v) >= ac.occupancy(vc), (name, v, vc)
             assert f"`fir_{kind}_kernel<{n}>` | {v} | {lds} |" in design, f"DESIGN.md section 17 states other figures than {v} VGPRs / {lds} B for fir_{kind}_kernel<{n}>"
     assert total == 10
 

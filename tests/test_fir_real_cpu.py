@@ -156,11 +156,6 @@ def _bodies(text, frag):
     return found
 
 
-def _occupancy(vgprs):
-    """waves per SIMD that the vector registers allow: 512 registers in granules of 8"""
-    return 512 // (-(-vgprs // 8) * 8)
-
-
 @pytest.fixture(scope="module")
 def isa(tmp_path_factory):
     """{N: assembly of smfft_fir_real_<N>.o as the Makefile compiles it}, and the assembly of the main library's smfft_fir.hip"""
@@ -222,7 +217,7 @@ def test_isa_budget_of_what_ships(isa):
         cname = next(k for k in cdescs if "fir_overlap_save_kernelILi%dE" % n in k)
         vc = ac.descriptor_field(cdescs, cname, "next_free_vgpr")
         print(f"N={n}: fir_real_overlap_save_kernel {v} VGPRs (complex bank: {vc}), fir_real_prepare_kernel {vp} VGPRs, {LDS_BYTES} B of LDS")
-        assert _occupancy(v) >= _occupancy(vc), (n, v, vc)
+        assert ac.occupancy(v) >= ac.occupancy(vc), (n, v, vc)
         assert f"`fir_real_overlap_save_kernel<{n}>` | {v} |" in design and f"`fir_real_prepare_kernel<{n}>` | {vp} |" in design, \
             f"DESIGN.md section 16 states other register counts than {v} / {vp} at N = {n}"
     assert total == 10

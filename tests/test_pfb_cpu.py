@@ -188,7 +188,7 @@ def test_replay_stores_once_and_loads_inside_the_window(case):
 def isa(tmp_path_factory):
     if not os.path.exists(HIPCC):
         pytest.skip("hipcc not installed")
-    return ac.pfb_isa("smfft_pfb", "PFB", tmp_path_factory.mktemp("pfb_isa"))
+    return ac.addon_isa("smfft_pfb", "PFB", ac.PFB_SIZES, tmp_path_factory.mktemp("pfb_isa"))
 
 
 def test_pfb_kernels_have_no_scratch_no_transcendentals_no_packed_f32(isa):

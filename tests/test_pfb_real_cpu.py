@@ -69,7 +69,7 @@ def test_model_is_the_lower_half_of_the_complex_banks_model(N):
 def isa(tmp_path_factory):
     if not os.path.exists(HIPCC):
         pytest.skip("hipcc not installed")
-    return ac.pfb_isa("smfft_pfb_real", "PFB_REAL", tmp_path_factory.mktemp("pfb_real_isa"))
+    return ac.addon_isa("smfft_pfb_real", "PFB_REAL", ac.PFB_SIZES, tmp_path_factory.mktemp("pfb_real_isa"))
 
 
 def test_kernels_fit_three_workgroups_per_cu_without_scratch(isa):

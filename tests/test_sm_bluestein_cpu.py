@@ -3,7 +3,6 @@
 table builder runs clean under the address and undefined-behaviour sanitizers as a stand-alone host program; the gfx950 code of the
 five kernels keeps the FIR bank's budget; and the C ABI declares, exports and validates the seven entry points without a device.  No GPU
 code is run (hipcc cross-compiles gfx950)."""
-import concurrent.futures
 import os
 import re
 import shutil
@@ -154,11 +153,6 @@ def test_table_builder_is_clean_under_asan_and_ubsan(tmp_path):
 
 
 # ---- 4: ISA budget and inventory -------------------------------------------------------------------------------
-def _occupancy(vgprs):
-    """waves per SIMD that the vector registers allow: 512 registers in granules of 8"""
-    return 512 // (-(-vgprs // 8) * 8)
-
-
 def _loop_depths(body):
     """per line of a kernel body, the loop depth of its basic block, from the annotations the compiler writes behind a block's label
     ("in Loop: Header=BB0_6 Depth=1", "This Inner Loop Header: Depth=2"); a block without one lies in no loop"""
@@ -179,13 +173,7 @@ def isa(tmp_path_factory):
     """{M: assembly of smfft_bluestein_<M>.o as the Makefile compiles it}"""
     if not os.path.exists(ac.HIPCC):
         pytest.skip("hipcc not installed")
-    tmp = tmp_path_factory.mktemp("bluestein_isa")
-
-    def compile_one(m):
-        return ac.device_asm(os.path.join(CSRC, "smfft_bluestein.hip"), ["-I" + CSRC] + ac.makefile_flags("BLUESTEIN", m) + [f"-DSMFFT_BLUESTEIN_N={m}"],
-                             tmp / f"smfft_bluestein_{m}.s")
-    with concurrent.futures.ThreadPoolExecutor(5) as pool:
-        return dict(zip(SIZES, pool.map(compile_one, SIZES)))
+    return ac.addon_isa("smfft_bluestein", "BLUESTEIN", SIZES, tmp_path_factory.mktemp("bluestein_isa"))
 
 
 def test_isa_budget_of_what_ships(isa):
@@ -206,9 +194,9 @@ def test_isa_budget_of_what_ships(isa):
         assert not [line for line in body if re.match(r"v_pk_(add|mul|fma)_f32", line)], name
         assert ac.descriptor_field(descs, name, "private_segment_fixed_size") == 0, name
         v, lds = ac.descriptor_field(descs, name, "next_free_vgpr"), ac.descriptor_field(descs, name, "group_segment_fixed_size")
-        print(f"M={m}: bluestein_kernel {v} VGPRs ({_occupancy(v)} waves per SIMD), {lds} B of LDS")
+        print(f"M={m}: bluestein_kernel {v} VGPRs ({ac.occupancy(v)} waves per SIMD), {lds} B of LDS")
         assert lds == LDS_BYTES, (name, lds)
-        assert v <= 256 and _occupancy(v) >= 2, (name, v)
+        assert v <= 256 and ac.occupancy(v) >= 2, (name, v)
         loads = [i for i, line in enumerate(body) if line.startswith("global_load") and re.search(r"\bnt\b", line)]
         assert len(loads) == 8 and all(re.match(r"global_load_dwordx2\s", body[i]) for i in loads), (name, len(loads))
         between = body[loads[0]:loads[-1] + 1]
@@ -249,8 +237,7 @@ def test_python_mirror_matches_header(bluestein_lib):
 
 
 def test_library_exports_exactly_the_seven_symbols(bluestein_lib):
-    nm = subprocess.run(["nm", "-D", "--defined-only", bluestein_lib], capture_output=True, text=True, check=True).stdout
-    assert sorted(re.findall(r" T (smfft_\w+)$", nm, re.M)) == sorted(NAMES)
+    ac.check_exports(bluestein_lib, NAMES)
 
 
 # ---- 6: rejections -------------------------------------------------------------------------------------------------
@@ -313,7 +300,4 @@ def test_python_wrappers_refuse_before_a_device(bluestein_lib):
 
 
 def test_import_does_not_load_the_library():
-    code = ("import sys; sys.path.insert(0, sys.argv[1]); import smfft_amd, smfft_amd.bluestein as l; assert l._lib is None; "
-            "maps = open('/proc/self/maps').read(); assert 'libsmfft_bluestein' not in maps; print('ok')")
-    p = subprocess.run([sys.executable, "-c", code, ROOT], capture_output=True, text=True, timeout=120)
-    assert p.returncode == 0 and "ok" in p.stdout, p.stdout + p.stderr
+    ac.check_import_does_not_load("bluestein", "smfft_bluestein")

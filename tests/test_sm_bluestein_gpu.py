@@ -20,6 +20,7 @@ import sys
 import numpy as np
 import pytest
 
+from tests import rows_gpu_harness as rh
 from tests.fir_gpu_harness import GRID_CAP, GUARD, ROW_MAX, ROW_REL_L2
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
@@ -30,7 +31,7 @@ pytestmark = pytest.mark.gpu
 SIZES = [256, 512, 1024, 2048, 4096]
 ENDS = [256, 4096]
 LENGTHS = {256: (1, 128), 512: (129, 256), 1024: (257, 512), 2048: (513, 1024), 4096: (1025, 2048)}      # (smallest, largest) n of M
-WORST = {}            # M -> [relL2, max / max]: the worst figures measured in this run
+WORST = rh.Worst()      # M -> [relL2, max / max]: the worst figures measured in this run
 
 
 @pytest.fixture(scope="module")
@@ -47,14 +48,6 @@ def bl():
     return bluestein
 
 
-def _rand(rng, shape):
-    return (rng.standard_normal(shape) + 1j * rng.standard_normal(shape)).astype(np.complex64)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
 def _want(x, inverse):
     x = x.astype(np.complex128)
     return np.fft.ifft(x, axis=-1) * x.shape[-1] if inverse else np.fft.fft(x, axis=-1)
@@ -66,8 +59,7 @@ def _check_rows(got, want, what, rel_l2=ROW_REL_L2):
     l2 = np.linalg.norm(d, axis=1) / np.maximum(np.linalg.norm(want, axis=1), 1e-30)
     mx = np.max(np.abs(d), axis=1) / np.maximum(np.max(np.abs(want), axis=1), 1e-30)
     m = bm.fft_size(got.shape[1])
-    worst = WORST.setdefault(m, [0.0, 0.0])
-    worst[0], worst[1] = max(worst[0], float(l2.max())), max(worst[1], float(mx.max()))
+    worst = WORST.record(m, l2, mx)
     print(f"{what}: worst row relL2 = {l2.max():.3e}, max |d| / max |want| = {mx.max():.3e}  (M = {m} so far: {worst[0]:.3e}, {worst[1]:.3e})")
     assert l2.max() <= rel_l2 and mx.max() <= ROW_MAX, f"{what}: row {int(np.argmax(l2))} relL2 = {l2.max():.3e}, row {int(np.argmax(mx))} max = {mx.max():.3e}"
 
@@ -84,35 +76,16 @@ class Plan:
         self.buf.free()
 
 
-def _guarded(sm, count, front=0):
-    """a device buffer of [front | count | GUARD] float2: 0x5A, 0xFF, 0x5A; returns (buffer, the payload's address)"""
-    buf = sm.DeviceBuffer((front + count + GUARD) * 8)
-    assert sm.lib.smfft_memset(buf.ptr, 0x5A, buf.nbytes) == 0
-    if count:
-        assert sm.lib.smfft_memset(buf.ptr + 8 * front, 0xFF, 8 * count) == 0
-    return buf, buf.ptr + 8 * front
-
-
-def _collect(buf, count, front=0, finite=True):
-    raw = buf.to_host(np.uint8, ((front + count + GUARD) * 8,))
-    assert np.all(raw[:8 * front] == 0x5A), "the kernel wrote in front of its output"
-    assert np.all(raw[8 * (front + count):] == 0x5A), "the kernel wrote past its output"
-    out = raw[8 * front:8 * (front + count)].view(np.complex64).copy()
-    if finite:
-        assert np.all(np.isfinite(out.view(np.float32))), "outputs left unwritten"
-    return out
-
-
 def run(sm, bl, x, inverse=False, front=0, finite=True, launch=None, in_place=False):
     """one launch through the device-pointer API on a copy of x = (batch, n) complex64 that ends where its allocation ends; returns the
-    (batch, n) result after checking the guards and (finite) that no NaN of the prefill is left.  front: elements between the output
-    allocation's start and the output's base; launch(din, dout, n, batch, plan): how to launch, when not on the null stream through the
+    (batch, n) result after checking the guards and (finite) that no NaN of the prefill is left.  front: elements between the output's
+    front guard and the output's base; launch(din, dout, n, batch, plan): how to launch, when not on the null stream through the
     mirror; in_place: the input is copied into the guarded buffer, which is input and output"""
     x = np.ascontiguousarray(x)
     assert x.dtype == np.complex64 and x.ndim == 2
     batch, n = x.shape
     plan = Plan(sm, bl, n, inverse)
-    dout, pout = _guarded(sm, batch * n, front)
+    dout, pout = rh.guarded(sm, batch * n, 8, front)
     if in_place:
         din, pin = None, pout
         assert sm.lib.smfft_memcpy_h2d(pout, x.ctypes.data, x.nbytes) == 0
@@ -126,7 +99,7 @@ def run(sm, bl, x, inverse=False, front=0, finite=True, launch=None, in_place=Fa
         else:
             launch(pin, pout, n, batch, plan.ptr)
         assert sm.lib.smfft_synchronize() == 0
-        return _collect(dout, batch * n, front, finite).reshape(batch, n)
+        return rh.collect(dout, batch * n, np.complex64, front, finite).reshape(batch, n)
     finally:
         for b in (din, dout, plan):
             if b is not None:
@@ -142,7 +115,7 @@ def _batch(n, tiles=2, extra=1):
 def test_against_fp64(sm, bl, n):
     """both sides of every M boundary, primes and powers of two; batch = 2F + 1 (two full tiles and one row), both directions"""
     rng = np.random.default_rng(n)
-    x = _rand(rng, (_batch(n), n))
+    x = rh.rand(rng, (_batch(n), n), np.complex64)
     for inverse in (False, True):
         _check_rows(run(sm, bl, x, inverse), _want(x, inverse), f"n={n} inverse={inverse}")
 
@@ -192,7 +165,7 @@ def test_probe_rows_are_isolated(sm, bl, M):
     n = LENGTHS[M][1]
     F = 4096 // M
     rng = np.random.default_rng(50 + M)
-    x = _rand(rng, (3 * F, n))
+    x = rh.rand(rng, (3 * F, n), np.complex64)
     clean = run(sm, bl, x)
     _check_rows(clean, _want(x, False), f"M={M} n={n} clean")
     whole, single = F + F // 2, 2 * F + F // 3
@@ -206,7 +179,7 @@ def test_probe_rows_are_isolated(sm, bl, M):
         got = run(sm, bl, bad, finite=False)
         assert np.isnan(got[row]).all(), (M, row, sample, int(np.isnan(got[row]).sum()))
         others = np.arange(3 * F) != row
-        assert np.array_equal(_bits(got[others]), _bits(clean[others])), (M, row, sample)
+        assert np.array_equal(rh.bits(got[others]), rh.bits(clean[others])), (M, row, sample)
 
 
 # ---- 5, 6: the grid -----------------------------------------------------------------------------------------------------------------
@@ -216,12 +189,12 @@ def test_grid_is_invisible(sm, bl, M):
     workgroup runs all six tiles with its tables held in registers"""
     n = LENGTHS[M][1]
     rng = np.random.default_rng(60 + M)
-    x = _rand(rng, (_batch(n, 5), n))
+    x = rh.rand(rng, (_batch(n, 5), n), np.complex64)
     base = run(sm, bl, x)
     _check_rows(base, _want(x, False), f"M={M} n={n} six tiles")
     for grid in (1, 2, 3, 6, 12288):
         got = run(sm, bl, x, launch=lambda din, dout, n_, batch, plan: bl.launch_tuned(din, dout, n_, batch, plan, grid))
-        assert np.array_equal(_bits(got), _bits(base)), (M, grid)
+        assert np.array_equal(rh.bits(got), rh.bits(base)), (M, grid)
 
 
 @pytest.mark.parametrize("n, batch", [(5, 16 * (2 * 12288) + 7), (1025, 2 * 12288 + 1)])
@@ -238,30 +211,30 @@ def test_grid_stride_loop(sm, bl, n, batch):
 @pytest.mark.parametrize("M", ENDS)
 def test_bounds(sm, bl, M):
     """n in {smallest, largest of M}, batch in {1, F - 1, F + 1}, the input ending where its allocation ends, the output base 1 and 3
-    elements inside its allocation: nothing in front of or behind the output changes, every output is written, and the bits are those
+    elements behind its front guard: nothing in front of or behind the output changes, every output is written, and the bits are those
     at the aligned base, which pass the fp64 bound"""
     F = 4096 // M
     rng = np.random.default_rng(70 + M)
     for n in LENGTHS[M]:
         for batch in sorted({1, max(1, F - 1), F + 1}):
-            x = _rand(rng, (batch, n))
+            x = rh.rand(rng, (batch, n), np.complex64)
             for inverse in (False, True):
                 base = run(sm, bl, x, inverse)
                 _check_rows(base, _want(x, inverse), f"M={M} n={n} batch={batch} inverse={inverse}")
                 for front in (1, 3):
                     got = run(sm, bl, x, inverse, front=front)
-                    assert np.array_equal(_bits(got), _bits(base)), f"M={M} n={n} batch={batch} front={front}: the result depends on placement"
+                    assert np.array_equal(rh.bits(got), rh.bits(base)), f"M={M} n={n} batch={batch} front={front}: the result depends on placement"
 
 
 @pytest.mark.parametrize("n", [129, 2047])
 def test_in_place(sm, bl, n):
     """d_out == d_in, batch = 2F + 1: the bits of the out-of-place run"""
     rng = np.random.default_rng(80 + n)
-    x = _rand(rng, (_batch(n), n))
+    x = rh.rand(rng, (_batch(n), n), np.complex64)
     for inverse in (False, True):
         base = run(sm, bl, x, inverse)
         _check_rows(base, _want(x, inverse), f"n={n} inverse={inverse} out of place")
-        assert np.array_equal(_bits(run(sm, bl, x, inverse, in_place=True)), _bits(base)), (n, inverse)
+        assert np.array_equal(rh.bits(run(sm, bl, x, inverse, in_place=True)), rh.bits(base)), (n, inverse)
 
 
 # ---- 9: 64-bit offsets ----------------------------------------------------------------------------------------------------------------
@@ -276,7 +249,7 @@ def test_offsets_beyond_two_to_the_31(sm, bl):
     rows = [0, straddle, batch - 2, batch - 1]
     zeros = [1, straddle // 2, straddle - 1, straddle + 1, batch - 3]
     rng = np.random.default_rng(31)
-    x = _rand(rng, (len(rows), n))
+    x = rh.rand(rng, (len(rows), n), np.complex64)
     total = batch * n
     buf = sm.DeviceBuffer((total + GUARD) * 8)
     plan = Plan(sm, bl, n, False)
@@ -297,7 +270,7 @@ def test_offsets_beyond_two_to_the_31(sm, bl):
         for r in zeros:
             row = np.empty(n, np.complex64)
             assert sm.lib.smfft_memcpy_d2h(row.ctypes.data, buf.ptr + r * n * 8, n * 8) == 0
-            words = _bits(row)
+            words = rh.bits(row)
             print(f"zero row {r}: {int(np.count_nonzero(words))} words that are not +0 ({int(np.count_nonzero(words == 0x80000000))} of them -0)")
             assert not words.any(), f"zero row {r} is not +0 everywhere"
     finally:
@@ -310,7 +283,7 @@ def test_offsets_beyond_two_to_the_31(sm, bl):
 def test_inverse_round_trip(sm, bl, n):
     """forward, then inverse, divided by n, returns x within 2 ROW_REL_L2 per row"""
     rng = np.random.default_rng(90 + n)
-    x = _rand(rng, (_batch(n), n))
+    x = rh.rand(rng, (_batch(n), n), np.complex64)
     back = run(sm, bl, run(sm, bl, x), inverse=True).astype(np.complex128) / n
     l2 = np.linalg.norm(back - x, axis=1) / np.linalg.norm(x.astype(np.complex128), axis=1)
     print(f"n={n}: worst round-trip relL2 = {l2.max():.3e}")
@@ -328,7 +301,7 @@ def test_caller_stream(sm, bl):
     assert hip.hipStreamCreate(ctypes.byref(stream)) == 0 and stream.value
     rng = np.random.default_rng(11)
     for n in (1000, 100):
-        x = _rand(rng, (37, n))
+        x = rh.rand(rng, (37, n), np.complex64)
         for inverse in (False, True):
             def launch(din, dout, n_, batch, plan):
                 mine = Plan(sm, bl, n_, inverse, stream=stream.value)       # (the run's own plan goes unused)
@@ -344,7 +317,7 @@ def test_benchmark_form_adds_to_the_timer(sm, bl):
     """the library's smfft_bluestein_benchmark adds its milliseconds to a non-zero total and fills the output; so does the mirror's"""
     n = 1536
     rng = np.random.default_rng(12)
-    x = _rand(rng, (300, n))
+    x = rh.rand(rng, (300, n), np.complex64)
     total = ctypes.c_double(1.0)
 
     def c_form(din, dout, n_, batch, plan):
@@ -356,7 +329,7 @@ def test_benchmark_form_adds_to_the_timer(sm, bl):
     def mirror(din, dout, n_, batch, plan):
         rc, ms = bl.benchmark(din, dout, n_, batch, plan)
         assert rc == 0 and ms > 0.0
-    assert np.array_equal(_bits(run(sm, bl, x, launch=mirror)), _bits(out))
+    assert np.array_equal(rh.bits(run(sm, bl, x, launch=mirror)), rh.bits(out))
 
 
 def test_host_round_trip(sm, bl):
@@ -365,16 +338,16 @@ def test_host_round_trip(sm, bl):
     x1 = rng.standard_normal(1000) + 1j * rng.standard_normal(1000)                  # 1-D complex128
     got = bl.fft(x1)
     assert got.shape == (1000,) and got.dtype == np.complex64
-    assert np.array_equal(_bits(got), _bits(run(sm, bl, x1.astype(np.complex64)[None])[0]))
+    assert np.array_equal(rh.bits(got), rh.bits(run(sm, bl, x1.astype(np.complex64)[None])[0]))
     _check_rows(got[None], _want(x1.astype(np.complex64)[None], False), "fft() 1-D")
-    x3 = _rand(rng, (2, 3, 257))
+    x3 = rh.rand(rng, (2, 3, 257), np.complex64)
     for inverse in (False, True):
         got = bl.fft(x3, inverse=inverse)
         assert got.shape == x3.shape and got.dtype == np.complex64
-        assert np.array_equal(_bits(got.reshape(6, 257)), _bits(run(sm, bl, x3.reshape(6, 257), inverse)))
+        assert np.array_equal(rh.bits(got.reshape(6, 257)), rh.bits(run(sm, bl, x3.reshape(6, 257), inverse)))
     xr = rng.standard_normal((4, 129))                                               # real float64
     got = bl.fft(xr)
     _check_rows(got, _want(xr.astype(np.float32).astype(np.complex64), False), "fft() real")
-    assert got.dtype == np.complex64 and np.array_equal(_bits(bl.fft(xr.astype(np.float32))), _bits(got))
+    assert got.dtype == np.complex64 and np.array_equal(rh.bits(bl.fft(xr.astype(np.float32))), rh.bits(got))
     assert bl.fft(np.zeros((0, 5), np.complex64)).shape == (0, 5)
     assert ROW_REL_L2 == 1e-6 and ROW_MAX == 5e-6

@@ -29,6 +29,7 @@ import sys
 import numpy as np
 import pytest
 
+from tests import rows_gpu_harness as rh
 from tests.fir_gpu_harness import GRID_CAP, GUARD, ROW_MAX, ROW_REL_L2
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
@@ -38,7 +39,7 @@ pytestmark = pytest.mark.gpu
 
 SIZES = [256, 512, 1024, 2048, 4096]
 LARGEST = {256: (128, 129), 512: (256, 257), 1024: (512, 513), 2048: (1024, 1025), 4096: (2048, 2048)}      # n + m - 1 = M (4095 at 4096)
-WORST = {}            # M -> [relL2, max / max]: the worst figures measured in this run
+WORST = rh.Worst()      # M -> [relL2, max / max]: the worst figures measured in this run
 
 
 def arcs(n):
@@ -64,14 +65,6 @@ def cz():
     return czt
 
 
-def _rand(rng, shape):
-    return (rng.standard_normal(shape) + 1j * rng.standard_normal(shape)).astype(np.complex64)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
 @functools.lru_cache(maxsize=3)
 def _kernel(n, m, start, step):
     """(n, m) complex128: exp(-2 pi i j (start + k step)), computed once per arc and shared, read only"""
@@ -89,7 +82,7 @@ def _rows(rng, batch, n, m, arc_list):
     """(x, wants): x (batch, n) complex64 Gaussian rows, each drawn again until ||want||_2 >= sqrt(m) ||x||_2 / 2 on every arc of
     arc_list (E ||want||_2^2 = m ||x||_2^2: every entry of the arc's matrix has modulus 1), and the fp64 references (batch, m), one per
     arc, computed here once"""
-    x = _rand(rng, (batch, n))
+    x = rh.rand(rng, (batch, n), np.complex64)
     wants = [np.empty((batch, m), np.complex128) for _ in arc_list]
     todo = np.arange(batch)
     while todo.size:
@@ -99,7 +92,7 @@ def _rows(rng, batch, n, m, arc_list):
             want[todo] = _want(x[todo], m, start, step)
             bad |= np.linalg.norm(want[todo], axis=1) < floor
         todo = todo[bad]
-        x[todo] = _rand(rng, (todo.size, n))
+        x[todo] = rh.rand(rng, (todo.size, n), np.complex64)
     return x, wants
 
 
@@ -109,8 +102,7 @@ def _check_rows(got, want, n, what, rel_l2=ROW_REL_L2):
     l2 = np.linalg.norm(d, axis=1) / np.maximum(np.linalg.norm(want, axis=1), 1e-30)
     mx = np.max(np.abs(d), axis=1) / np.maximum(np.max(np.abs(want), axis=1), 1e-30)
     M = cm.fft_size(n, got.shape[1])
-    worst = WORST.setdefault(M, [0.0, 0.0])
-    worst[0], worst[1] = max(worst[0], float(l2.max())), max(worst[1], float(mx.max()))
+    worst = WORST.record(M, l2, mx)
     print(f"{what}: worst row relL2 = {l2.max():.3e}, max |d| / max |want| = {mx.max():.3e}  (M = {M} so far: {worst[0]:.3e}, {worst[1]:.3e})")
     assert l2.max() <= rel_l2 and mx.max() <= ROW_MAX, f"{what}: row {int(np.argmax(l2))} relL2 = {l2.max():.3e}, row {int(np.argmax(mx))} max = {mx.max():.3e}"
 
@@ -127,27 +119,6 @@ class Plan:
         self.buf.free()
 
 
-def _guarded(sm, count, front=0):
-    """a device buffer of [GUARD + front | count | GUARD] float2: 0x5A, 0xFF, 0x5A; returns (buffer, the payload's address)"""
-    front += GUARD
-    buf = sm.DeviceBuffer((front + count + GUARD) * 8)
-    assert sm.lib.smfft_memset(buf.ptr, 0x5A, buf.nbytes) == 0
-    if count:
-        assert sm.lib.smfft_memset(buf.ptr + 8 * front, 0xFF, 8 * count) == 0
-    return buf, buf.ptr + 8 * front
-
-
-def _collect(buf, count, front=0, finite=True):
-    front += GUARD
-    raw = buf.to_host(np.uint8, ((front + count + GUARD) * 8,))
-    assert np.all(raw[:8 * front] == 0x5A), "the kernel wrote in front of its output"
-    assert np.all(raw[8 * (front + count):] == 0x5A), "the kernel wrote past its output"
-    out = raw[8 * front:8 * (front + count)].view(np.complex64).copy()
-    if finite:
-        assert np.all(np.isfinite(out.view(np.float32))), "outputs left unwritten"
-    return out
-
-
 def run(sm, cz, x, m, start, step, front=0, finite=True, launch=None, in_place=False):
     """one launch through the device-pointer API on a copy of x = (batch, n) complex64 that ends where its allocation ends; returns the
     (batch, m) result after checking the guards and (finite) that no NaN of the prefill is left.  front: elements between the output's
@@ -157,7 +128,7 @@ def run(sm, cz, x, m, start, step, front=0, finite=True, launch=None, in_place=F
     assert x.dtype == np.complex64 and x.ndim == 2
     batch, n = x.shape
     plan = Plan(sm, cz, n, m, start, step)
-    dout, pout = _guarded(sm, batch * m, front)
+    dout, pout = rh.guarded(sm, batch * m, 8, front)
     if in_place:
         assert m == n
         din, pin = None, pout
@@ -172,7 +143,7 @@ def run(sm, cz, x, m, start, step, front=0, finite=True, launch=None, in_place=F
         else:
             launch(pin, pout, n, m, batch, plan.ptr)
         assert sm.lib.smfft_synchronize() == 0
-        return _collect(dout, batch * m, front, finite).reshape(batch, m)
+        return rh.collect(dout, batch * m, np.complex64, front, finite).reshape(batch, m)
     finally:
         for b in (din, dout, plan):
             if b is not None:
@@ -266,7 +237,7 @@ def test_probe_rows_are_isolated(sm, cz, n, m):
         got = run(sm, cz, bad, m, start, step, finite=False)
         assert got.shape == (3 * F, m) and np.isnan(got[row]).all(), (n, m, row, sample, int(np.isnan(got[row]).sum()))
         others = np.arange(3 * F) != row
-        assert np.array_equal(_bits(got[others]), _bits(clean[others])), (n, m, row, sample)
+        assert np.array_equal(rh.bits(got[others]), rh.bits(clean[others])), (n, m, row, sample)
 
 
 # ---- 5, 6: the grid -----------------------------------------------------------------------------------------------------------------
@@ -283,7 +254,7 @@ def test_grid_is_invisible(sm, cz, M):
     _check_rows(base, want, n, f"M={M} n={n} m={m} six tiles")
     for grid in (1, 2, 3, 6, 12288):
         got = run(sm, cz, x, m, start, step, launch=lambda din, dout, n_, m_, batch, plan: cz.launch_tuned(din, dout, n_, m_, batch, plan, grid))
-        assert np.array_equal(_bits(got), _bits(base)), (M, grid)
+        assert np.array_equal(rh.bits(got), rh.bits(base)), (M, grid)
 
 
 @pytest.mark.parametrize("n, m, batch", [(5, 3, 16 * (2 * 12288) + 7), (1025, 1024, 2 * 12288 + 1)])
@@ -313,7 +284,7 @@ def test_bounds(sm, cz, n, m):
         _check_rows(base, want, n, f"n={n} m={m} batch={batch}")
         for front in (1, 3):
             got = run(sm, cz, x, m, start, step, front=front)
-            assert np.array_equal(_bits(got), _bits(base)), f"n={n} m={m} batch={batch} front={front}: the result depends on placement"
+            assert np.array_equal(rh.bits(got), rh.bits(base)), f"n={n} m={m} batch={batch} front={front}: the result depends on placement"
 
 
 @pytest.mark.parametrize("n", [129, 2047])
@@ -324,7 +295,7 @@ def test_in_place(sm, cz, n):
     x, (want,) = _rows(rng, _batch(n, n), n, n, [(start, step)])
     base = run(sm, cz, x, n, start, step)
     _check_rows(base, want, n, f"n=m={n} out of place")
-    assert np.array_equal(_bits(run(sm, cz, x, n, start, step, in_place=True)), _bits(base)), n
+    assert np.array_equal(rh.bits(run(sm, cz, x, n, start, step, in_place=True)), rh.bits(base)), n
 
 
 # ---- 8: 64-bit offsets ----------------------------------------------------------------------------------------------------------------
@@ -364,14 +335,14 @@ def test_offsets_beyond_two_to_the_31(sm, cz, n, m):
         if m == 1:
             whole = np.empty(batch, np.complex64)
             assert sm.lib.smfft_memcpy_d2h(whole.ctypes.data, dout.ptr, whole.nbytes) == 0
-            words = _bits(np.delete(whole, rows))
+            words = rh.bits(np.delete(whole, rows))
             print(f"{words.size // 2} zero rows: {int(np.count_nonzero(words))} words that are not +0")
             assert not words.any(), "a zero row is not +0"
         else:
             for r in zeros:
                 row = np.empty(m, np.complex64)
                 assert sm.lib.smfft_memcpy_d2h(row.ctypes.data, dout.ptr + r * m * 8, m * 8) == 0
-                words = _bits(row)
+                words = rh.bits(row)
                 print(f"zero row {r}: {int(np.count_nonzero(words))} words that are not +0 ({int(np.count_nonzero(words == 0x80000000))} of them -0)")
                 assert not words.any(), f"zero row {r} is not +0 everywhere"
     finally:
@@ -420,7 +391,7 @@ def test_benchmark_form_adds_to_the_timer(sm, cz):
     def mirror(din, dout, n_, m_, batch, plan):
         rc, ms = cz.benchmark(din, dout, n_, m_, batch, plan)
         assert rc == 0 and ms > 0.0
-    assert np.array_equal(_bits(run(sm, cz, x, m, start, step, launch=mirror)), _bits(out))
+    assert np.array_equal(rh.bits(run(sm, cz, x, m, start, step, launch=mirror)), rh.bits(out))
 
 
 def test_host_round_trip(sm, cz):
@@ -430,20 +401,20 @@ def test_host_round_trip(sm, cz):
     x1 = rng.standard_normal(1000) + 1j * rng.standard_normal(1000)                  # 1-D complex128
     got = cz.czt(x1)
     assert got.shape == (1000,) and got.dtype == np.complex64
-    assert np.array_equal(_bits(got), _bits(run(sm, cz, x1.astype(np.complex64)[None], 1000, 0.0, 1.0 / 1000)[0]))
+    assert np.array_equal(rh.bits(got), rh.bits(run(sm, cz, x1.astype(np.complex64)[None], 1000, 0.0, 1.0 / 1000)[0]))
     _check_rows(got[None], np.fft.fft(x1.astype(np.complex64).astype(np.complex128))[None], 1000, "czt() 1-D, the defaults")
     got = cz.czt(x1, m=24, start=0.1, step=1e-4)
     assert got.shape == (24,) and got.dtype == np.complex64
-    assert np.array_equal(_bits(got), _bits(run(sm, cz, x1.astype(np.complex64)[None], 24, 0.1, 1e-4)[0]))
-    x3 = _rand(rng, (2, 3, 257))
+    assert np.array_equal(rh.bits(got), rh.bits(run(sm, cz, x1.astype(np.complex64)[None], 24, 0.1, 1e-4)[0]))
+    x3 = rh.rand(rng, (2, 3, 257), np.complex64)
     got = cz.czt(x3, m=100, start=-0.2, step=-0.013)
     assert got.shape == (2, 3, 100) and got.dtype == np.complex64
-    assert np.array_equal(_bits(got.reshape(6, 100)), _bits(run(sm, cz, x3.reshape(6, 257), 100, -0.2, -0.013)))
+    assert np.array_equal(rh.bits(got.reshape(6, 100)), rh.bits(run(sm, cz, x3.reshape(6, 257), 100, -0.2, -0.013)))
     xr = rng.standard_normal((4, 129))                                               # real float64
     got = cz.czt(xr, m=130, start=0.37)
     _check_rows(got, _want(xr.astype(np.float32).astype(np.complex64), 130, 0.37, 1.0 / 129), 129, "czt() real")
     assert got.dtype == np.complex64 and got.shape == (4, 130)
-    assert np.array_equal(_bits(cz.czt(xr.astype(np.float32), m=130, start=0.37)), _bits(got))
+    assert np.array_equal(rh.bits(cz.czt(xr.astype(np.float32), m=130, start=0.37)), rh.bits(got))
     empty = cz.czt(np.zeros((0, 5), np.complex64), m=3)
     assert empty.shape == (0, 3) and empty.dtype == np.complex64
     assert ROW_REL_L2 == 1e-6 and ROW_MAX == 5e-6

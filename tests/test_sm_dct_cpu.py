@@ -2,7 +2,6 @@
 is the fp64 sum of the definition for all four transforms, and in fp32 stays inside the GPU tests' bounds; the generated twiddle octant
 is the committed one and its symmetries give fp64 values rounded once; the gfx950 code of the ten kernels keeps its budget; and the C
 ABI declares, exports and validates the four entry points without a device.  No GPU code is run (hipcc cross-compiles gfx950)."""
-import concurrent.futures
 import os
 import re
 import subprocess
@@ -117,27 +116,19 @@ def test_twiddle_octant_is_the_generated_one():
     assert np.max(np.abs(c.astype(np.float64) - np.cos(ang))) <= 1.01 * 2.0 ** -25
     assert np.max(np.abs(s.astype(np.float64) - np.sin(ang))) <= 1.01 * 2.0 ** -25
     assert c[0] == 1 and s[0] == 0 and c[8192] == 0 and s[8192] == 1 and c[4096] == s[4096]
-    source = open(os.path.join(CSRC, "smfft_dct.hip")).read()
+    # the table and its symmetries live in the header that the four half-length row libraries share
+    source = open(os.path.join(CSRC, "smfft_rows.hpp")).read()
     assert "smfft/smfft_twiddles_dct.inc" in source and "b.y, b.x" in source and "-a.y, a.x" in source and "-b.x, b.y" in source
+    assert '#include "smfft_rows.hpp"' in open(os.path.join(CSRC, "smfft_dct.hip")).read()
 
 
 # ---- 2: ISA budget and inventory -------------------------------------------------------------------------------
-def _occupancy(vgprs):
-    """waves per SIMD that the vector registers allow: 512 registers in granules of 8"""
-    return 512 // (-(-vgprs // 8) * 8)
-
-
 @pytest.fixture(scope="module")
 def isa(tmp_path_factory):
     """{M: assembly of smfft_dct_<M>.o as the Makefile compiles it}"""
     if not os.path.exists(ac.HIPCC):
         pytest.skip("hipcc not installed")
-    tmp = tmp_path_factory.mktemp("dct_isa")
-
-    def compile_one(m):
-        return ac.device_asm(os.path.join(CSRC, "smfft_dct.hip"), ["-I" + CSRC] + ac.makefile_flags("DCT", m) + [f"-DSMFFT_DCT_N={m}"], tmp / f"smfft_dct_{m}.s")
-    with concurrent.futures.ThreadPoolExecutor(5) as pool:
-        return dict(zip(SIZES, pool.map(compile_one, SIZES)))
+    return ac.addon_isa("smfft_dct", "DCT", SIZES, tmp_path_factory.mktemp("dct_isa"))
 
 
 def test_isa_budget_of_what_ships(isa):
@@ -159,9 +150,9 @@ def test_isa_budget_of_what_ships(isa):
             assert not [line for line in body if re.match(r"v_pk_(add|mul|fma)_f32", line)], name
             assert ac.descriptor_field(descs, name, "private_segment_fixed_size") == 0, name
             v, lds = ac.descriptor_field(descs, name, "next_free_vgpr"), ac.descriptor_field(descs, name, "group_segment_fixed_size")
-            print(f"M={m}: {'dct2_kernel' if 'dct2' in name else 'dct3_kernel'} {v} VGPRs ({_occupancy(v)} waves per SIMD), {lds} B of LDS, 0 B of scratch")
+            print(f"M={m}: {'dct2_kernel' if 'dct2' in name else 'dct3_kernel'} {v} VGPRs ({ac.occupancy(v)} waves per SIMD), {lds} B of LDS, 0 B of scratch")
             assert lds == LDS_BUDGET and 2 * lds <= ac.LDS_PER_CU, (name, lds)
-            assert v <= 256 and _occupancy(v) >= 2, (name, v)
+            assert v <= 256 and ac.occupancy(v) >= 2, (name, v)
             # the row accesses: type II loads and type III stores eight 16-byte quads per thread, non-temporal (but for type III's at
             # M = 2048); type II stores and type III loads thirty-two floats, plain (the other loads, 8 bytes each, are twiddles)
             two = "dct2" in name
@@ -188,10 +179,7 @@ def test_library_ships_ten_kernels_and_the_inventory_names_them(dct_lib):
 def test_isa_identity_compares_the_library():
     """tools/isa_identity.py compiles the five objects with the Makefile's flags and -I., like the other add-ons' (the tool itself
     needs the history of a git checkout and minutes of compiling: it is run by hand, DESIGN.md section 22 has its verdict)"""
-    import isa_identity
-    assert ("smfft_dct", "DCT", SIZES, True) in isa_identity.ADDONS
-    names = [u[0] for u in isa_identity.units(ROOT)]
-    assert all(f"smfft_dct_{m}" in names for m in SIZES) and len(names) == len(set(names))
+    ac.check_isa_identity_lists("smfft_dct", "DCT", SIZES)
 
 
 # ---- 3: declarations and exports ---------------------------------------------------------------------------------
@@ -214,8 +202,7 @@ def test_python_mirror_matches_header(dct_lib):
 
 
 def test_library_exports_exactly_the_four_symbols(dct_lib):
-    nm = subprocess.run(["nm", "-D", "--defined-only", dct_lib], capture_output=True, text=True, check=True).stdout
-    assert sorted(re.findall(r" T (smfft_\w+)$", nm, re.M)) == sorted(NAMES)
+    ac.check_exports(dct_lib, NAMES)
 
 
 # ---- 4: rejections -------------------------------------------------------------------------------------------------
@@ -270,18 +257,12 @@ sys.exit(0 if rc and rc == [-1] * len(rc) and empty == [0] * 360 and t.value == 
 def test_python_wrappers_refuse_before_a_device(dct_lib):
     """in a process where no GPU is visible: the pointer forms turn the library's -1 into a RuntimeError, the array forms raise
     ValueError or TypeError themselves, and an empty batch is served"""
-    code = r"""
+    code = ac.REFUSED + r"""
 import sys
 sys.path.insert(0, sys.argv[1])
 import numpy as np
 from smfft_amd import dct
 IN, OUT = 1 << 20, 1 << 30
-def refused(exc, f, *a, **k):
-    try:
-        f(*a, **k)
-    except exc:
-        return
-    raise SystemExit(f"{f.__name__}{a}{k} was not refused with {exc.__name__}")
 for n in (256, 500, 16384, 0):
     refused(RuntimeError, dct.launch_ptr, IN, OUT, n, 10)
     refused(RuntimeError, dct.launch_tuned, IN, OUT, n, 10, 3)
@@ -313,7 +294,4 @@ print("ok")
 
 
 def test_import_does_not_load_the_library():
-    code = ("import sys; sys.path.insert(0, sys.argv[1]); import smfft_amd, smfft_amd.dct as l; assert l._lib is None; "
-            "maps = open('/proc/self/maps').read(); assert 'libsmfft_dct' not in maps; print('ok')")
-    p = subprocess.run([sys.executable, "-c", code, ROOT], capture_output=True, text=True, timeout=120)
-    assert p.returncode == 0 and "ok" in p.stdout, p.stdout + p.stderr
+    ac.check_import_does_not_load("dct", "smfft_dct")

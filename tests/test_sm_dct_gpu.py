@@ -24,6 +24,7 @@ import numpy as np
 import pytest
 
 from tests import guarded_region
+from tests import rows_gpu_harness as rh
 from tests.fir_gpu_harness import GRID_CAP, GUARD, ROW_MAX, ROW_REL_L2
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
@@ -33,7 +34,7 @@ pytestmark = pytest.mark.gpu
 
 LENGTHS = [512, 1024, 2048, 4096, 8192]
 TRANSFORMS = [(2, False), (3, False), (2, True), (3, True)]       # (type, sine)
-WORST = {}                  # n -> [relL2, max / max]: the worst figures measured in this run
+WORST = rh.Worst()      # n -> [relL2, max / max]: the worst figures measured in this run
 E = 4                       # bytes per element
 
 
@@ -51,14 +52,6 @@ def dc():
     return dct
 
 
-def _rand(rng, shape):
-    return rng.standard_normal(shape).astype(np.float32)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
 def _name(type, sine):
     return f"{'DST' if sine else 'DCT'}-{'II' if type == 2 else 'III'}"
 
@@ -72,30 +65,10 @@ def _check_rows(got, want, n, what, factor=1.0):
     d = got.astype(np.float64) - want
     l2 = np.linalg.norm(d, axis=1) / np.maximum(np.linalg.norm(want, axis=1), 1e-300)
     mx = np.max(np.abs(d), axis=1) / np.maximum(np.max(np.abs(want), axis=1), 1e-300)
-    worst = WORST.setdefault(n, [0.0, 0.0])
-    worst[0], worst[1] = max(worst[0], float(l2.max())), max(worst[1], float(mx.max()))
+    worst = WORST.record(n, l2, mx)
     print(f"{what}: worst row relL2 = {l2.max():.3e}, max |d| / max |want| = {mx.max():.3e}  (n = {n} so far: {worst[0]:.3e}, {worst[1]:.3e})")
     assert l2.max() <= factor * ROW_REL_L2 and mx.max() <= factor * ROW_MAX, \
         f"{what}: row {int(np.argmax(l2))} relL2 = {l2.max():.3e}, row {int(np.argmax(mx))} max = {mx.max():.3e}"
-
-
-def _guarded(sm, count):
-    """a device buffer of [GUARD | count | GUARD] float32: 0x5A, 0xFF, 0x5A; returns (buffer, the payload's address)"""
-    buf = sm.DeviceBuffer((count + 2 * GUARD) * E)
-    assert sm.lib.smfft_memset(buf.ptr, 0x5A, buf.nbytes) == 0
-    if count:
-        assert sm.lib.smfft_memset(buf.ptr + E * GUARD, 0xFF, E * count) == 0
-    return buf, buf.ptr + E * GUARD
-
-
-def _collect(buf, count, finite=True):
-    raw = buf.to_host(np.uint8, ((count + 2 * GUARD) * E,))
-    assert np.all(raw[:E * GUARD] == 0x5A), "the kernel wrote in front of its output"
-    assert np.all(raw[E * (GUARD + count):] == 0x5A), "the kernel wrote past its output"
-    out = raw[E * GUARD:E * (GUARD + count)].view(np.float32).copy()
-    if finite:
-        assert np.all(np.isfinite(out)), "outputs left unwritten"
-    return out
 
 
 def run(sm, dc, x, type, sine, finite=True, launch=None, in_place=False):
@@ -106,7 +79,7 @@ def run(sm, dc, x, type, sine, finite=True, launch=None, in_place=False):
     x = np.ascontiguousarray(x)
     assert x.dtype == np.float32 and x.ndim == 2
     batch, n = x.shape
-    dout, pout = _guarded(sm, batch * n)
+    dout, pout = rh.guarded(sm, batch * n, E)
     din = None
     try:
         if in_place:
@@ -121,7 +94,7 @@ def run(sm, dc, x, type, sine, finite=True, launch=None, in_place=False):
         else:
             launch(pin, pout, n, batch, type, sine)
         assert sm.lib.smfft_synchronize() == 0
-        return _collect(dout, batch * n, finite).reshape(batch, n)
+        return rh.collect(dout, batch * n, np.float32, finite=finite).reshape(batch, n)
     finally:
         for buf in (din, dout):
             if buf is not None:
@@ -136,7 +109,7 @@ def test_against_fp64(sm, dc, n, type, sine, which):
     """batch = 1 (a single row), 17 (a ragged last tile at sixteen rows per workgroup, several tiles above) and 8192 / n + 1 (one row
     past a full tile)"""
     batch = (1, 17, _ffts(n) + 1)[which]
-    x = _rand(np.random.default_rng(10 * n + batch), (batch, n))
+    x = rh.rand(np.random.default_rng(10 * n + batch), (batch, n))
     got = run(sm, dc, x, type, sine)
     assert got.shape == (batch, n) and got.dtype == np.float32
     _check_rows(got, dm.chain(x, type, sine), n, f"n={n} {_name(type, sine)} batch={batch}")
@@ -160,7 +133,7 @@ def test_probe_impulses(sm, dc, n):
 @pytest.mark.parametrize("n", LENGTHS)
 def test_round_trip(sm, dc, n):
     """DCT-III(DCT-II(x)) / (2n) and DST-III(DST-II(x)) / (2n) return x within twice the row bounds (two launches), batch = 8192 / n + 1"""
-    x = _rand(np.random.default_rng(20 + n), (_ffts(n) + 1, n))
+    x = rh.rand(np.random.default_rng(20 + n), (_ffts(n) + 1, n))
     for sine in (False, True):
         forward = run(sm, dc, x, 2, sine)
         back = run(sm, dc, forward, 3, sine)
@@ -174,7 +147,7 @@ def test_probe_rows_are_isolated(sm, dc, n):
     in every element or nearly: each output is a sum over the whole row) and every other row keeps the bits of the clean run"""
     F = _ffts(n)
     batch = 2 * F + 1
-    x = _rand(np.random.default_rng(30 + n), (batch, n))
+    x = rh.rand(np.random.default_rng(30 + n), (batch, n))
     row = F + F // 2
     for type, sine in TRANSFORMS:
         clean = run(sm, dc, x, type, sine)
@@ -188,7 +161,7 @@ def test_probe_rows_are_isolated(sm, dc, n):
             got = run(sm, dc, bad, type, sine, finite=False)
             assert not np.isfinite(got[row]).all(), (n, type, sine, case)
             others = np.arange(batch) != row
-            assert np.array_equal(_bits(got[others]), _bits(clean[others])), (n, type, sine, case)
+            assert np.array_equal(rh.bits(got[others]), rh.bits(clean[others])), (n, type, sine, case)
 
 
 @pytest.mark.parametrize("n", LENGTHS)
@@ -199,8 +172,8 @@ def test_position_grid_and_in_place_are_invisible(sm, dc, n):
     F = _ffts(n)
     batch = 3 * F + 1
     rng = np.random.default_rng(40 + n)
-    probe = _rand(rng, (1, n))
-    x = _rand(rng, (batch, n))
+    probe = rh.rand(rng, (1, n))
+    x = rh.rand(rng, (batch, n))
     places = sorted({0, F - 1, F + F // 2, batch - 1})
     x[places] = probe[0]
     for type, sine in TRANSFORMS:
@@ -208,13 +181,13 @@ def test_position_grid_and_in_place_are_invisible(sm, dc, n):
         _check_rows(alone, dm.chain(probe, type, sine), n, f"n={n} {_name(type, sine)} alone")
         base = run(sm, dc, x, type, sine)
         for r in places:
-            assert np.array_equal(_bits(base[r]), _bits(alone[0])), (n, type, sine, r)
+            assert np.array_equal(rh.bits(base[r]), rh.bits(alone[0])), (n, type, sine, r)
         for grid in (1, 3):
             got = run(sm, dc, x, type, sine, launch=lambda i, o, nn, b, t, s: dc.launch_tuned(i, o, nn, b, grid, t, s))
-            assert np.array_equal(_bits(got), _bits(base)), (n, type, sine, grid)
-        assert np.array_equal(_bits(run(sm, dc, x, type, sine, in_place=True)), _bits(base)), (n, type, sine, "in place")
+            assert np.array_equal(rh.bits(got), rh.bits(base)), (n, type, sine, grid)
+        assert np.array_equal(rh.bits(run(sm, dc, x, type, sine, in_place=True)), rh.bits(base)), (n, type, sine, "in place")
         got = run(sm, dc, x, type, sine, in_place=True, launch=lambda i, o, nn, b, t, s: dc.launch_tuned(i, o, nn, b, 1, t, s))
-        assert np.array_equal(_bits(got), _bits(base)), (n, type, sine, "in place, one workgroup")
+        assert np.array_equal(rh.bits(got), rh.bits(base)), (n, type, sine, "in place, one workgroup")
 
 
 # ---- 4: the grid-stride loop ----------------------------------------------------------------------------------------------------------
@@ -226,7 +199,7 @@ def test_grid_stride_loop(sm, dc, type, sine):
     n, F = 512, 16
     batch = F * (2 * GRID_CAP) + 7
     assert GRID_CAP == 12288 and GRID_CAP < -(-batch // F) <= 3 * GRID_CAP and batch % F
-    block = _rand(np.random.default_rng(50 + type), (4096, n))
+    block = rh.rand(np.random.default_rng(50 + type), (4096, n))
     want = dm.chain(block, type, sine)
     din, dout = sm.DeviceBuffer(batch * n * E), sm.DeviceBuffer((batch * n + GUARD) * E)
     try:
@@ -261,7 +234,7 @@ def test_bounds(sm, dc, n, batch):
     transforms: the input and everything around it are unchanged, nothing around the batch * n output floats is written, every output
     is, and the bits are those of the plain run, which passes the fp64 bound.  (A read outside the input would pick up the poison, a
     NaN, and show in the result.)"""
-    x = _rand(np.random.default_rng(60 + n), (batch, n))
+    x = rh.rand(np.random.default_rng(60 + n), (batch, n))
     for type, sine in TRANSFORMS:
         base = run(sm, dc, x, type, sine)
         _check_rows(base, dm.chain(x, type, sine), n, f"n={n} batch={batch} {_name(type, sine)}")
@@ -272,7 +245,7 @@ def test_bounds(sm, dc, n, batch):
             assert sm.lib.smfft_synchronize() == 0
             rin.outside_unchanged(whole=True)
             got = rout.outside_unchanged(whole=False).view(np.float32).reshape(batch, n)
-            assert np.array_equal(_bits(got), _bits(base)), (n, batch, type, sine)
+            assert np.array_equal(rh.bits(got), rh.bits(base)), (n, batch, type, sine)
         finally:
             rin.buf.free()
             rout.buf.free()
@@ -289,7 +262,7 @@ def test_offsets_beyond_two_to_the_31(sm, dc, type, sine):
     assert (batch - 8) * n == 1 << 31
     rows = [0, 1, (1 << 29) // n - 1, (1 << 29) // n, (1 << 30) // n - 1, (1 << 30) // n, (1 << 31) // n - 1, (1 << 31) // n, batch - 2, batch - 1]
     zeros = [2, (1 << 29) // n + 1, (1 << 31) // n - 2, (1 << 31) // n + 1, batch - 3]
-    x = _rand(np.random.default_rng(70 + type), (len(rows), n))
+    x = rh.rand(np.random.default_rng(70 + type), (len(rows), n))
     want = dm.chain(x, type, sine)
     buf = sm.DeviceBuffer((batch * n + GUARD) * E)
     try:
@@ -325,7 +298,7 @@ def test_caller_stream(sm, dc):
     assert hip.hipStreamCreate(ctypes.byref(stream)) == 0 and stream.value
     rng = np.random.default_rng(11)
     for n, type, sine in ((1024, 2, True), (4096, 3, False)):
-        x = _rand(rng, (37, n))
+        x = rh.rand(rng, (37, n))
 
         def launch(din, dout, nn, batch, t, s):
             assert sm.lib.smfft_synchronize() == 0                              # the prefill of the output, on the null stream
@@ -338,7 +311,7 @@ def test_caller_stream(sm, dc):
 def test_benchmark_form_adds_to_the_timer(sm, dc):
     """the library's smfft_dct_benchmark adds its milliseconds to a non-zero total and fills the output; so does the mirror's"""
     n = 2048
-    x = _rand(np.random.default_rng(12), (300, n))
+    x = rh.rand(np.random.default_rng(12), (300, n))
     total = ctypes.c_double(1.0)
 
     def c_form(din, dout, nn, batch, t, s):
@@ -350,7 +323,7 @@ def test_benchmark_form_adds_to_the_timer(sm, dc):
     def mirror(din, dout, nn, batch, t, s):
         status, ms = dc.benchmark(din, dout, nn, batch, t, s)
         assert status == 0 and ms > 0.0
-    assert np.array_equal(_bits(run(sm, dc, x, 2, False, launch=mirror)), _bits(out))
+    assert np.array_equal(rh.bits(run(sm, dc, x, 2, False, launch=mirror)), rh.bits(out))
 
 
 def test_host_round_trip(sm, dc):
@@ -360,13 +333,13 @@ def test_host_round_trip(sm, dc):
     x1 = rng.standard_normal(1024)                                                  # 1-D float64
     got = dc.dct(x1)
     assert got.shape == (1024,) and got.dtype == np.float32
-    assert np.array_equal(_bits(got), _bits(run(sm, dc, x1.astype(np.float32)[None], 2, False)[0]))
+    assert np.array_equal(rh.bits(got), rh.bits(run(sm, dc, x1.astype(np.float32)[None], 2, False)[0]))
     _check_rows(got[None], dm.chain(x1.astype(np.float32)[None], 2, False), 1024, "dct() 1-D")
-    x3 = _rand(rng, (2, 3, 512))
+    x3 = rh.rand(rng, (2, 3, 512))
     for type in (2, 3):
         got = dc.dst(x3, type=type)
         assert got.shape == x3.shape and got.dtype == np.float32
-        assert np.array_equal(_bits(got.reshape(6, 512)), _bits(run(sm, dc, x3.reshape(6, 512), type, True)))
+        assert np.array_equal(rh.bits(got.reshape(6, 512)), rh.bits(run(sm, dc, x3.reshape(6, 512), type, True)))
     back = dc.dct(dc.dct(x3), type=3) / np.float32(2 * 512)
     _check_rows(back.reshape(6, 512), x3.reshape(6, 512).astype(np.float64), 512, "dct(dct(x), 3) / 2n", factor=2.0)
     empty = dc.dct(np.zeros((0, 512), np.float32))
@@ -384,20 +357,20 @@ def test_tensors_on_the_device(sm, dc):
     the bits of the device-pointer launch; a tensor that is not contiguous float32 is refused"""
     import torch
     rng = np.random.default_rng(8)
-    x = _rand(rng, (5, 3, 2048))
+    x = rh.rand(rng, (5, 3, 2048))
     t = torch.from_numpy(x).cuda()
     for type, sine in TRANSFORMS:
         want = run(sm, dc, x.reshape(15, 2048), type, sine).reshape(x.shape)
         got = (dc.dst if sine else dc.dct)(t, type=type)
         assert got.shape == t.shape and got.dtype == torch.float32 and got.is_cuda and got.data_ptr() != t.data_ptr()
         torch.cuda.synchronize()
-        assert np.array_equal(_bits(got.cpu().numpy()), _bits(want)), (type, sine)
+        assert np.array_equal(rh.bits(got.cpu().numpy()), rh.bits(want)), (type, sine)
         out = torch.full_like(t, float("nan"))
         assert dc.launch(t, out, type=type, sine=sine) is out
         work = t.clone()
         assert dc.launch(work, work, type=type, sine=sine) is work
         torch.cuda.synchronize()
-        assert np.array_equal(_bits(out.cpu().numpy()), _bits(want)) and np.array_equal(_bits(work.cpu().numpy()), _bits(want)), (type, sine)
+        assert np.array_equal(rh.bits(out.cpu().numpy()), rh.bits(want)) and np.array_equal(rh.bits(work.cpu().numpy()), rh.bits(want)), (type, sine)
     with pytest.raises(TypeError):
         dc.launch(t.double())
     with pytest.raises(ValueError):

@@ -2,7 +2,6 @@
 in fp64 is the definition through the full-length DFT and scipy.signal.hilbert for the three kinds, and in fp32 stays inside the GPU
 tests' bounds; the gfx950 code of the fifteen kernels keeps its budget; and the C ABI declares, exports and validates the four entry
 points without a device.  No GPU code is run (hipcc cross-compiles gfx950)."""
-import concurrent.futures
 import os
 import re
 import subprocess
@@ -98,23 +97,12 @@ def test_fp32_model_is_inside_the_bounds():
 
 
 # ---- 2: ISA budget and inventory -------------------------------------------------------------------------------
-def _occupancy(vgprs):
-    """waves per SIMD that the vector registers allow: 512 registers in granules of 8"""
-    return 512 // (-(-vgprs // 8) * 8)
-
-
 @pytest.fixture(scope="module")
 def isa(tmp_path_factory):
     """{M: assembly of smfft_hilbert_<M>.o as the Makefile compiles it}"""
     if not os.path.exists(ac.HIPCC):
         pytest.skip("hipcc not installed")
-    tmp = tmp_path_factory.mktemp("hilbert_isa")
-
-    def compile_one(m):
-        flags = ["-I" + CSRC] + ac.makefile_flags("HILBERT", m) + [f"-DSMFFT_HILBERT_N={m}"]
-        return ac.device_asm(os.path.join(CSRC, "smfft_hilbert.hip"), flags, tmp / f"smfft_hilbert_{m}.s")
-    with concurrent.futures.ThreadPoolExecutor(5) as pool:
-        return dict(zip(SIZES, pool.map(compile_one, SIZES)))
+    return ac.addon_isa("smfft_hilbert", "HILBERT", SIZES, tmp_path_factory.mktemp("hilbert_isa"))
 
 
 def test_isa_budget_of_what_ships(isa):
@@ -141,9 +129,9 @@ def test_isa_budget_of_what_ships(isa):
             assert not [line for line in body if re.match(r"v_pk_(add|mul|fma)_f32", line)], name
             assert ac.descriptor_field(descs, name, "private_segment_fixed_size") == 0, name
             v, lds = ac.descriptor_field(descs, name, "next_free_vgpr"), ac.descriptor_field(descs, name, "group_segment_fixed_size")
-            print(f"M={m}: hilbert_kernel<{m}, {kind}> {v} VGPRs ({_occupancy(v)} waves per SIMD), {lds} B of LDS, 0 B of scratch")
+            print(f"M={m}: hilbert_kernel<{m}, {kind}> {v} VGPRs ({ac.occupancy(v)} waves per SIMD), {lds} B of LDS, 0 B of scratch")
             assert LDS_BUDGET <= lds <= LDS_BUDGET + 64 and 2 * lds <= ac.LDS_PER_CU, (name, lds)
-            assert v <= 256 and _occupancy(v) >= 2, (name, v)
+            assert v <= 256 and ac.occupancy(v) >= 2, (name, v)
             # the row loads are the non-temporal ones (the others, plain, are twiddles)
             loads = [i for i, line in enumerate(body) if line.startswith("global_load") and re.search(r"\bnt\b", line)]
             every_load = [i for i, line in enumerate(body) if line.startswith("global_load")]
@@ -172,10 +160,7 @@ def test_library_ships_fifteen_kernels_and_the_inventory_names_them(hilbert_lib)
 def test_isa_identity_compares_the_library():
     """tools/isa_identity.py compiles the five objects with the Makefile's flags and -I., like the other add-ons' (the tool itself
     needs the history of a git checkout and minutes of compiling: it is run by hand, DESIGN.md section 23 has its verdict)"""
-    import isa_identity
-    assert ("smfft_hilbert", "HILBERT", SIZES, True) in isa_identity.ADDONS
-    names = [u[0] for u in isa_identity.units(ROOT)]
-    assert all(f"smfft_hilbert_{m}" in names for m in SIZES) and len(names) == len(set(names))
+    ac.check_isa_identity_lists("smfft_hilbert", "HILBERT", SIZES)
 
 
 # ---- 3: declarations and exports ---------------------------------------------------------------------------------
@@ -206,8 +191,7 @@ def test_python_mirror_matches_header(hilbert_lib):
 
 
 def test_library_exports_exactly_the_four_symbols(hilbert_lib):
-    nm = subprocess.run(["nm", "-D", "--defined-only", hilbert_lib], capture_output=True, text=True, check=True).stdout
-    assert sorted(re.findall(r" T (smfft_\w+)$", nm, re.M)) == sorted(NAMES)
+    ac.check_exports(hilbert_lib, NAMES)
 
 
 # ---- 4: rejections -------------------------------------------------------------------------------------------------
@@ -263,18 +247,12 @@ sys.exit(0 if ok else 1)
 def test_python_wrappers_refuse_before_a_device(hilbert_lib):
     """in a process where no GPU is visible: the pointer forms turn the library's -1 into a RuntimeError, the array forms raise
     ValueError or TypeError themselves, and an empty batch is served"""
-    code = r"""
+    code = ac.REFUSED + r"""
 import sys
 sys.path.insert(0, sys.argv[1])
 import numpy as np
 from smfft_amd import hilbert as hb
 IN, OUT = 1 << 20, 1 << 30
-def refused(exc, f, *a, **k):
-    try:
-        f(*a, **k)
-    except exc:
-        return
-    raise SystemExit(f"{f.__name__}{a}{k} was not refused with {exc.__name__}")
 for n in (256, 500, 16384, 0):
     refused(RuntimeError, hb.launch_ptr, IN, OUT, n, 10)
     refused(RuntimeError, hb.launch_tuned, IN, OUT, n, 10, 3)
@@ -310,7 +288,4 @@ print("ok")
 
 
 def test_import_does_not_load_the_library():
-    code = ("import sys; sys.path.insert(0, sys.argv[1]); import smfft_amd, smfft_amd.hilbert as l; assert l._lib is None; "
-            "maps = open('/proc/self/maps').read(); assert 'libsmfft_hilbert' not in maps; print('ok')")
-    p = subprocess.run([sys.executable, "-c", code, ROOT], capture_output=True, text=True, timeout=120)
-    assert p.returncode == 0 and "ok" in p.stdout, p.stdout + p.stderr
+    ac.check_import_does_not_load("hilbert", "smfft_hilbert")

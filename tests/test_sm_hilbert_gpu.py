@@ -23,6 +23,7 @@ import numpy as np
 import pytest
 
 from tests import guarded_region
+from tests import rows_gpu_harness as rh
 from tests.fir_gpu_harness import GRID_CAP, GUARD, ROW_MAX, ROW_REL_L2
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
@@ -33,7 +34,7 @@ pytestmark = pytest.mark.gpu
 LENGTHS = [512, 1024, 2048, 4096, 8192]
 KINDS = [0, 1, 2]
 NAMES = {0: "quadrature", 1: "analytic", 2: "envelope"}
-WORST = {}                  # n -> [relL2, max / max]: the worst figures measured in this run
+WORST = rh.Worst()      # n -> [relL2, max / max]: the worst figures measured in this run
 E = 4                       # bytes per element
 
 
@@ -49,14 +50,6 @@ def hb():
     from smfft_amd import hilbert
     hilbert.lib()
     return hilbert
-
-
-def _rand(rng, shape):
-    return rng.standard_normal(shape).astype(np.float32)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def _ffts(n):
@@ -76,30 +69,10 @@ def _check_rows(got, want, x, what):
     x = x.astype(np.float64)
     l2 = np.linalg.norm(d, axis=1) / np.maximum(np.linalg.norm(x, axis=1), 1e-300)
     mx = np.max(d, axis=1) / np.maximum(np.max(np.abs(x), axis=1), 1e-300)
-    worst = WORST.setdefault(n, [0.0, 0.0])
-    worst[0], worst[1] = max(worst[0], float(l2.max())), max(worst[1], float(mx.max()))
+    worst = WORST.record(n, l2, mx)
     print(f"{what}: worst row relL2 = {l2.max():.3e}, max |d| / max |x| = {mx.max():.3e}  (n = {n} so far: {worst[0]:.3e}, {worst[1]:.3e})")
     assert l2.max() <= ROW_REL_L2 and mx.max() <= ROW_MAX, \
         f"{what}: row {int(np.argmax(l2))} relL2 = {l2.max():.3e}, row {int(np.argmax(mx))} max = {mx.max():.3e}"
-
-
-def _guarded(sm, count):
-    """a device buffer of [GUARD | count | GUARD] float32: 0x5A, 0xFF, 0x5A; returns (buffer, the payload's address)"""
-    buf = sm.DeviceBuffer((count + 2 * GUARD) * E)
-    assert sm.lib.smfft_memset(buf.ptr, 0x5A, buf.nbytes) == 0
-    if count:
-        assert sm.lib.smfft_memset(buf.ptr + E * GUARD, 0xFF, E * count) == 0
-    return buf, buf.ptr + E * GUARD
-
-
-def _collect(buf, count, finite=True):
-    raw = buf.to_host(np.uint8, ((count + 2 * GUARD) * E,))
-    assert np.all(raw[:E * GUARD] == 0x5A), "the kernel wrote in front of its output"
-    assert np.all(raw[E * (GUARD + count):] == 0x5A), "the kernel wrote past its output"
-    out = raw[E * GUARD:E * (GUARD + count)].view(np.float32).copy()
-    if finite:
-        assert np.all(np.isfinite(out)), "outputs left unwritten"
-    return out
 
 
 def _shape(flat, batch, n, kind):
@@ -115,7 +88,7 @@ def run(sm, hb, x, kind, finite=True, launch=None, in_place=False):
     assert x.dtype == np.float32 and x.ndim == 2 and not (in_place and kind == 1)
     batch, n = x.shape
     count = batch * n * _width(kind)
-    dout, pout = _guarded(sm, count)
+    dout, pout = rh.guarded(sm, count, E)
     din = None
     try:
         if in_place:
@@ -130,7 +103,7 @@ def run(sm, hb, x, kind, finite=True, launch=None, in_place=False):
         else:
             launch(pin, pout, n, batch, kind)
         assert sm.lib.smfft_synchronize() == 0
-        return _shape(_collect(dout, count, finite), batch, n, kind)
+        return _shape(rh.collect(dout, count, np.float32, finite=finite), batch, n, kind)
     finally:
         for buf in (din, dout):
             if buf is not None:
@@ -142,10 +115,10 @@ def _inputs(n, batch, which):
     own per row, with a phase, under a mean of 1000"""
     rng = np.random.default_rng(10 * n + which)
     if which == 0:
-        return _rand(rng, (batch, n))
+        return rh.rand(rng, (batch, n))
     if which == 1:
         exps = np.round(np.linspace(-40, 40, batch)).astype(np.int64)
-        return np.ldexp(_rand(rng, (batch, n)), exps[:, None].astype(np.int32)).astype(np.float32)
+        return np.ldexp(rh.rand(rng, (batch, n)), exps[:, None].astype(np.int32)).astype(np.float32)
     bins = rng.integers(1, n // 2, batch)
     phase = rng.uniform(0, 2 * np.pi, batch)
     return (1000.0 + np.cos(2 * np.pi * np.outer(bins, np.arange(n)) / n + phase[:, None])).astype(np.float32)
@@ -164,7 +137,7 @@ def test_against_fp64(sm, hb, n, kind, which):
     assert got.shape == (batch, n) and got.dtype == (np.complex64 if kind == 1 else np.float32)
     _check_rows(got, hm.chain(x, kind), x, f"n={n} {NAMES[kind]} inputs {which} batch={batch}")
     if kind == 1:
-        assert np.array_equal(_bits(got.real), _bits(x))
+        assert np.array_equal(rh.bits(got.real), rh.bits(x))
 
 
 # ---- 2: exact probes ----------------------------------------------------------------------------------------------------------------
@@ -225,7 +198,7 @@ def test_probe_rows_are_isolated(sm, hb, n):
     nearly: every output is a sum over the whole row) and every other row keeps the bits of the clean run"""
     F = _ffts(n)
     batch = 2 * F + 1
-    x = _rand(np.random.default_rng(30 + n), (batch, n))
+    x = rh.rand(np.random.default_rng(30 + n), (batch, n))
     row = F + F // 2
     for kind in KINDS:
         clean = run(sm, hb, x, kind)
@@ -241,7 +214,7 @@ def test_probe_rows_are_isolated(sm, hb, n):
             print(f"n={n} {NAMES[kind]} {case}: {int(np.isfinite(part).sum())} of {n} outputs of the row are finite")
             assert not np.isfinite(part).all(), (n, kind, case)
             others = np.arange(batch) != row
-            assert np.array_equal(_bits(got[others]), _bits(clean[others])), (n, kind, case)
+            assert np.array_equal(rh.bits(got[others]), rh.bits(clean[others])), (n, kind, case)
 
 
 @pytest.mark.parametrize("n", LENGTHS)
@@ -252,8 +225,8 @@ def test_position_grid_and_in_place_are_invisible(sm, hb, n):
     F = _ffts(n)
     batch = 3 * F + 1
     rng = np.random.default_rng(40 + n)
-    probe = _rand(rng, (1, n))
-    x = _rand(rng, (batch, n))
+    probe = rh.rand(rng, (1, n))
+    x = rh.rand(rng, (batch, n))
     places = sorted({0, F - 1, F + F // 2, batch - 1})
     x[places] = probe[0]
     for kind in KINDS:
@@ -261,14 +234,14 @@ def test_position_grid_and_in_place_are_invisible(sm, hb, n):
         _check_rows(alone, hm.chain(probe, kind), probe, f"n={n} {NAMES[kind]} alone")
         base = run(sm, hb, x, kind)
         for r in places:
-            assert np.array_equal(_bits(base[r]), _bits(alone[0])), (n, kind, r)
+            assert np.array_equal(rh.bits(base[r]), rh.bits(alone[0])), (n, kind, r)
         for grid in (1, 3):
             got = run(sm, hb, x, kind, launch=lambda i, o, nn, b, k: hb.launch_tuned(i, o, nn, b, grid, k))
-            assert np.array_equal(_bits(got), _bits(base)), (n, kind, grid)
+            assert np.array_equal(rh.bits(got), rh.bits(base)), (n, kind, grid)
         if kind != 1:
-            assert np.array_equal(_bits(run(sm, hb, x, kind, in_place=True)), _bits(base)), (n, kind, "in place")
+            assert np.array_equal(rh.bits(run(sm, hb, x, kind, in_place=True)), rh.bits(base)), (n, kind, "in place")
             got = run(sm, hb, x, kind, in_place=True, launch=lambda i, o, nn, b, k: hb.launch_tuned(i, o, nn, b, 1, k))
-            assert np.array_equal(_bits(got), _bits(base)), (n, kind, "in place, one workgroup")
+            assert np.array_equal(rh.bits(got), rh.bits(base)), (n, kind, "in place, one workgroup")
 
 
 # ---- 4: the grid-stride loop ----------------------------------------------------------------------------------------------------------
@@ -280,7 +253,7 @@ def test_grid_stride_loop(sm, hb, kind):
     n, F, W = 512, 16, _width(kind)
     batch = F * (2 * GRID_CAP) + 7
     assert GRID_CAP == 12288 and GRID_CAP < -(-batch // F) <= 3 * GRID_CAP and batch % F
-    block = _rand(np.random.default_rng(50 + kind), (4096, n))
+    block = rh.rand(np.random.default_rng(50 + kind), (4096, n))
     want = hm.chain(block, kind)
     din, dout = sm.DeviceBuffer(batch * n * E), sm.DeviceBuffer((batch * n * W + GUARD) * E)
     try:
@@ -316,7 +289,7 @@ def test_bounds(sm, hb, n, batch):
     kinds: the input and everything around it are unchanged, nothing around the output's elements is written, every one of them is, and
     the bits are those of the plain run, which passes the fp64 bound.  (A read outside the input would pick up the poison, a NaN, and
     show in the result.)"""
-    x = _rand(np.random.default_rng(60 + n), (batch, n))
+    x = rh.rand(np.random.default_rng(60 + n), (batch, n))
     for kind in KINDS:
         base = run(sm, hb, x, kind)
         _check_rows(base, hm.chain(x, kind), x, f"n={n} batch={batch} {NAMES[kind]}")
@@ -327,7 +300,7 @@ def test_bounds(sm, hb, n, batch):
             assert sm.lib.smfft_synchronize() == 0
             rin.outside_unchanged(whole=True)
             got = rout.outside_unchanged(whole=False).view(np.float32)
-            assert np.array_equal(_bits(got), _bits(base).reshape(-1)), (n, batch, kind)
+            assert np.array_equal(rh.bits(got), rh.bits(base).reshape(-1)), (n, batch, kind)
         finally:
             rin.buf.free()
             rout.buf.free()
@@ -337,7 +310,7 @@ def test_adjacent_buffers_are_served(sm, hb):
     """n = 1024, batch = 9: input and output in one allocation, the output right behind the input and right in front of it -- the
     nearest ranges that the overlap check must not refuse -- give the bits of the plain run, and the input is unchanged"""
     n, batch = 1024, 9
-    x = _rand(np.random.default_rng(65), (batch, n))
+    x = rh.rand(np.random.default_rng(65), (batch, n))
     for kind in KINDS:
         base = run(sm, hb, x, kind)
         count = batch * n * _width(kind)
@@ -351,7 +324,7 @@ def test_adjacent_buffers_are_served(sm, hb):
                 got, back = np.empty(count, np.float32), np.empty_like(x)
                 assert sm.lib.smfft_memcpy_d2h(got.ctypes.data, pout, got.nbytes) == 0
                 assert sm.lib.smfft_memcpy_d2h(back.ctypes.data, pin, back.nbytes) == 0
-                assert np.array_equal(_bits(got), _bits(base).reshape(-1)) and np.array_equal(_bits(back), _bits(x)), kind
+                assert np.array_equal(rh.bits(got), rh.bits(base).reshape(-1)) and np.array_equal(rh.bits(back), rh.bits(x)), kind
         finally:
             buf.free()
 
@@ -366,7 +339,7 @@ def test_offsets_beyond_two_to_the_31(sm, hb):
     assert (batch - 8) * n == 1 << 31
     rows = [0, 1, (1 << 29) // n - 1, (1 << 29) // n, (1 << 30) // n - 1, (1 << 30) // n, (1 << 31) // n - 1, (1 << 31) // n, batch - 2, batch - 1]
     zeros = [2, (1 << 29) // n + 1, (1 << 31) // n - 2, (1 << 31) // n + 1, batch - 3]
-    x = _rand(np.random.default_rng(70), (len(rows), n))
+    x = rh.rand(np.random.default_rng(70), (len(rows), n))
     want = hm.chain(x, kind)
     buf = sm.DeviceBuffer((batch * n + GUARD) * E)
     try:
@@ -402,7 +375,7 @@ def test_caller_stream(sm, hb):
     assert hip.hipStreamCreate(ctypes.byref(stream)) == 0 and stream.value
     rng = np.random.default_rng(11)
     for n, kind in ((1024, 1), (4096, 2)):
-        x = _rand(rng, (37, n))
+        x = rh.rand(rng, (37, n))
 
         def launch(din, dout, nn, batch, k):
             assert sm.lib.smfft_synchronize() == 0                              # the prefill of the output, on the null stream
@@ -415,7 +388,7 @@ def test_caller_stream(sm, hb):
 def test_benchmark_form_adds_to_the_timer(sm, hb):
     """the library's smfft_hilbert_benchmark adds its milliseconds to a non-zero total and fills the output; so does the mirror's"""
     n = 2048
-    x = _rand(np.random.default_rng(12), (300, n))
+    x = rh.rand(np.random.default_rng(12), (300, n))
     total = ctypes.c_double(1.0)
 
     def c_form(din, dout, nn, batch, k):
@@ -427,7 +400,7 @@ def test_benchmark_form_adds_to_the_timer(sm, hb):
     def mirror(din, dout, nn, batch, k):
         status, ms = hb.benchmark(din, dout, nn, batch, k)
         assert status == 0 and ms > 0.0
-    assert np.array_equal(_bits(run(sm, hb, x, 0, launch=mirror)), _bits(out))
+    assert np.array_equal(rh.bits(run(sm, hb, x, 0, launch=mirror)), rh.bits(out))
 
 
 def test_host_round_trip(sm, hb):
@@ -438,16 +411,16 @@ def test_host_round_trip(sm, hb):
     x1 = rng.standard_normal(1024)                                                  # 1-D float64
     got = hb.hilbert(x1)
     assert got.shape == (1024,) and got.dtype == np.float32
-    assert np.array_equal(_bits(got), _bits(run(sm, hb, x1.astype(np.float32)[None], 0)[0]))
+    assert np.array_equal(rh.bits(got), rh.bits(run(sm, hb, x1.astype(np.float32)[None], 0)[0]))
     _check_rows(got[None], hm.chain(x1.astype(np.float32)[None], 0), x1[None], "hilbert() 1-D")
-    x3 = _rand(rng, (2, 3, 512))
+    x3 = rh.rand(rng, (2, 3, 512))
     for kind, fn, dtype in ((0, hb.hilbert, np.float32), (1, hb.analytic, np.complex64), (2, hb.envelope, np.float32)):
         got = fn(x3)
         assert got.shape == x3.shape and got.dtype == dtype
-        assert np.array_equal(_bits(got.reshape(6, 512)), _bits(run(sm, hb, x3.reshape(6, 512), kind)))
+        assert np.array_equal(rh.bits(got.reshape(6, 512)), rh.bits(run(sm, hb, x3.reshape(6, 512), kind)))
     a = hb.analytic(torch.from_numpy(x3))
     assert isinstance(a, torch.Tensor) and not a.is_cuda and a.dtype == torch.complex64 and a.shape == x3.shape
-    assert np.array_equal(_bits(a.numpy()), _bits(hb.analytic(x3))) and np.array_equal(_bits(a.numpy().real), _bits(x3))
+    assert np.array_equal(rh.bits(a.numpy()), rh.bits(hb.analytic(x3))) and np.array_equal(rh.bits(a.numpy().real), rh.bits(x3))
     for fn, dtype in ((hb.hilbert, np.float32), (hb.analytic, np.complex64)):
         empty = fn(np.zeros((0, 512), np.float32))
         assert empty.shape == (0, 512) and empty.dtype == dtype
@@ -463,7 +436,7 @@ def test_tensors_on_the_device(sm, hb):
     float32, an out of the wrong dtype or shape and the analytic kind in place are refused"""
     import torch
     rng = np.random.default_rng(8)
-    x = _rand(rng, (5, 3, 2048))
+    x = rh.rand(rng, (5, 3, 2048))
     t = torch.from_numpy(x).cuda()
     for kind, fn in ((0, hb.hilbert), (1, hb.analytic), (2, hb.envelope)):
         dtype = torch.complex64 if kind == 1 else torch.float32
@@ -471,16 +444,16 @@ def test_tensors_on_the_device(sm, hb):
         got = fn(t)
         assert got.shape == t.shape and got.dtype == dtype and got.is_cuda and got.data_ptr() != t.data_ptr()
         torch.cuda.synchronize()
-        assert np.array_equal(_bits(got.cpu().numpy()), _bits(want)), kind
+        assert np.array_equal(rh.bits(got.cpu().numpy()), rh.bits(want)), kind
         out = torch.full(t.shape, float("nan"), dtype=dtype, device="cuda")
         assert hb.launch(t, out, kind=kind) is out
         torch.cuda.synchronize()
-        assert np.array_equal(_bits(out.cpu().numpy()), _bits(want)), kind
+        assert np.array_equal(rh.bits(out.cpu().numpy()), rh.bits(want)), kind
         if kind != 1:
             work = t.clone()
             assert hb.launch(work, work, kind=kind) is work
             torch.cuda.synchronize()
-            assert np.array_equal(_bits(work.cpu().numpy()), _bits(want)), kind
+            assert np.array_equal(rh.bits(work.cpu().numpy()), rh.bits(want)), kind
     with pytest.raises(TypeError):
         hb.launch(t.double())
     with pytest.raises(ValueError):

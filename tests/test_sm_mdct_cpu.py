@@ -3,7 +3,6 @@ in fp64 is the fp64 sum of the definition and scipy's type 4 transforms, the MDC
 in fp32 the chain stays inside the GPU tests' bounds; the fold and the unfold cover every sample once; the generated twiddle table is
 the committed one and its symmetric extension gives fp64 values rounded once; the gfx950 code of the fifteen kernels keeps its budget;
 and the C ABI declares, exports and validates the ten entry points without a device.  No GPU code is run (hipcc cross-compiles gfx950)."""
-import concurrent.futures
 import os
 import re
 import subprocess
@@ -157,29 +156,22 @@ def test_twiddle_table_is_the_generated_one():
     # what the rows index: (4p+1) 8192 / n of W_65536 and k 16384 / n of W_32768 stay inside the quarter and the half circle
     for n in LENGTHS:
         assert (4 * (n // 2 - 1) + 1) * (8192 // n) < 16384 and (n // 2 - 1) * (16384 // n) < 16384
-    source = open(os.path.join(CSRC, "smfft_mdct.hip")).read()
-    assert "smfft/smfft_twiddles_mdct.inc" in source and "smfft/smfft_twiddles_dct.inc" in source
+    # W_65536 is this library's own; W_32768 comes from the header that the four half-length row libraries share
+    source, shared = open(os.path.join(CSRC, "smfft_mdct.hip")).read(), open(os.path.join(CSRC, "smfft_rows.hpp")).read()
+    assert '#include "smfft/smfft_twiddles_mdct.inc"' in source and '#include "smfft_rows.hpp"' in source
+    assert '#include "smfft/smfft_twiddles_dct.inc"' in shared
     assert "TwiddleValue{b.y, b.x}" in source and "odd_octant_65536[(16384 - m - 1) / 2]" in source
-    assert not re.search(r"\b(sinf?|cosf?|sincosf?|__sinf|__cosf)\s*\(", re.sub(r"//[^\n]*", "", source))
+    for text in (source, shared):
+        assert not re.search(r"\b(sinf?|cosf?|sincosf?|__sinf|__cosf)\s*\(", re.sub(r"//[^\n]*", "", text))
 
 
 # ---- 2: ISA budget and inventory -------------------------------------------------------------------------------
-def _occupancy(vgprs):
-    """waves per SIMD that the vector registers allow: 512 registers in granules of 8"""
-    return 512 // (-(-vgprs // 8) * 8)
-
-
 @pytest.fixture(scope="module")
 def isa(tmp_path_factory):
     """{M: assembly of smfft_mdct_<M>.o as the Makefile compiles it}"""
     if not os.path.exists(ac.HIPCC):
         pytest.skip("hipcc not installed")
-    tmp = tmp_path_factory.mktemp("mdct_isa")
-
-    def compile_one(m):
-        return ac.device_asm(os.path.join(CSRC, "smfft_mdct.hip"), ["-I" + CSRC] + ac.makefile_flags("MDCT", m) + [f"-DSMFFT_MDCT_N={m}"], tmp / f"smfft_mdct_{m}.s")
-    with concurrent.futures.ThreadPoolExecutor(5) as pool:
-        return dict(zip(SIZES, pool.map(compile_one, SIZES)))
+    return ac.addon_isa("smfft_mdct", "MDCT", SIZES, tmp_path_factory.mktemp("mdct_isa"))
 
 
 def test_isa_budget_of_what_ships(isa):
@@ -204,9 +196,9 @@ def test_isa_budget_of_what_ships(isa):
             assert not [line for line in body if re.match(r"v_(sin|cos)_", line)], name
             assert ac.descriptor_field(descs, name, "private_segment_fixed_size") == 0, name
             v, lds = ac.descriptor_field(descs, name, "next_free_vgpr"), ac.descriptor_field(descs, name, "group_segment_fixed_size")
-            print(f"M={m}: {family}_kernel {v} VGPRs ({_occupancy(v)} waves per SIMD), {lds} B of LDS, 0 B of scratch")
+            print(f"M={m}: {family}_kernel {v} VGPRs ({ac.occupancy(v)} waves per SIMD), {lds} B of LDS, 0 B of scratch")
             assert lds == LDS_BUDGET and 2 * lds <= ac.LDS_PER_CU, (name, lds)
-            assert v <= 256 and _occupancy(v) >= 2, (name, v)
+            assert v <= 256 and ac.occupancy(v) >= 2, (name, v)
             # the row (and window) accesses are the 16-byte ones; the 8-byte loads are twiddles
             loads = [i for i, line in enumerate(body) if re.match(r"global_load_dwordx4\s", line)]
             stores = [i for i, line in enumerate(body) if line.startswith("global_store")]
@@ -230,10 +222,7 @@ def test_library_ships_fifteen_kernels_and_the_inventory_names_them(mdct_lib):
 def test_isa_identity_compares_the_library():
     """tools/isa_identity.py compiles the five objects with the Makefile's flags and -I., like the other add-ons' (the tool itself
     needs the history of a git checkout and minutes of compiling: it is run by hand, DESIGN.md section 24 has its verdict)"""
-    import isa_identity
-    assert ("smfft_mdct", "MDCT", SIZES, True) in isa_identity.ADDONS
-    names = [u[0] for u in isa_identity.units(ROOT)]
-    assert all(f"smfft_mdct_{m}" in names for m in SIZES) and len(names) == len(set(names))
+    ac.check_isa_identity_lists("smfft_mdct", "MDCT", SIZES)
     assert all("-ffp-contract=on" in ac.makefile_flags("MDCT", m) for m in SIZES)
 
 
@@ -262,8 +251,8 @@ def test_python_mirror_matches_header(mdct_lib):
 
 
 def test_library_exports_exactly_the_ten_symbols(mdct_lib):
-    nm = subprocess.run(["nm", "-D", "--defined-only", mdct_lib], capture_output=True, text=True, check=True).stdout
-    assert sorted(re.findall(r" T (smfft_\w+)$", nm, re.M)) == sorted(NAMES) and len(NAMES) == 10
+    ac.check_exports(mdct_lib, NAMES)
+    assert len(NAMES) == 10
 
 
 # ---- 4: rejections -------------------------------------------------------------------------------------------------
@@ -334,18 +323,12 @@ sys.exit(0 if rc and rc == [-1] * len(rc) and empty and empty == [0] * len(empty
 def test_python_wrappers_refuse_before_a_device(mdct_lib):
     """in a process where no GPU is visible: the pointer forms turn the library's -1 into a RuntimeError, the tensor and array forms
     raise ValueError or TypeError themselves, and a zero count is served"""
-    code = r"""
+    code = ac.REFUSED + r"""
 import sys
 sys.path.insert(0, sys.argv[1])
 import numpy as np
 from smfft_amd import mdct
 IN, OUT, WIN = 1 << 30, 1 << 40, 1 << 20
-def refused(exc, f, *a, **k):
-    try:
-        f(*a, **k)
-    except exc:
-        return
-    raise SystemExit(f"{f.__name__}{a}{k} was not refused with {exc.__name__}")
 for n in (256, 500, 16384, 0):
     refused(RuntimeError, mdct.launch_ptr, IN, OUT, n, 10)
     refused(RuntimeError, mdct.dct4_ptr, IN, OUT, n, 10, grid=3)
@@ -403,7 +386,4 @@ print("ok")
 
 
 def test_import_does_not_load_the_library():
-    code = ("import sys; sys.path.insert(0, sys.argv[1]); import smfft_amd, smfft_amd.mdct as l; assert l._lib is None; "
-            "maps = open('/proc/self/maps').read(); assert 'libsmfft_mdct' not in maps; print('ok')")
-    p = subprocess.run([sys.executable, "-c", code, ROOT], capture_output=True, text=True, timeout=120)
-    assert p.returncode == 0 and "ok" in p.stdout, p.stdout + p.stderr
+    ac.check_import_does_not_load("mdct", "smfft_mdct")

@@ -24,6 +24,7 @@ import numpy as np
 import pytest
 
 from tests import guarded_region
+from tests import rows_gpu_harness as rh
 from tests.fir_gpu_harness import GUARD, ROW_MAX, ROW_REL_L2
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
@@ -33,7 +34,7 @@ pytestmark = pytest.mark.gpu
 
 LENGTHS = [512, 1024, 2048, 4096, 8192]
 KINDS = ["dct4", "dst4", "mdct", "mdct_flat", "imdct"]       # mdct_flat: the MDCT with a NULL window
-WORST = {}                  # kind -> [relL2, max / max]: the worst figures measured in this run
+WORST = rh.Worst()      # kind -> [relL2, max / max]: the worst figures measured in this run
 E = 4                       # bytes per element
 
 
@@ -49,14 +50,6 @@ def md():
     from smfft_amd import mdct
     mdct.lib()              # a missing library raises here: the tests fail, they do not skip
     return mdct
-
-
-def _rand(rng, shape):
-    return rng.standard_normal(shape).astype(np.float32)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def _ffts(n):
@@ -86,30 +79,10 @@ def _check_rows(got, want, kind, what, factor=1.0):
     d = got.astype(np.float64) - want
     l2 = np.linalg.norm(d, axis=1) / np.maximum(np.linalg.norm(want, axis=1), 1e-300)
     mx = np.max(np.abs(d), axis=1) / np.maximum(np.max(np.abs(want), axis=1), 1e-300)
-    worst = WORST.setdefault(kind, [0.0, 0.0])
-    worst[0], worst[1] = max(worst[0], float(l2.max())), max(worst[1], float(mx.max()))
+    worst = WORST.record(kind, l2, mx)
     print(f"{what}: worst row relL2 = {l2.max():.3e}, max |d| / max |want| = {mx.max():.3e}  ({kind} so far: {worst[0]:.3e}, {worst[1]:.3e})")
     assert l2.max() <= factor * ROW_REL_L2 and mx.max() <= factor * ROW_MAX, \
         f"{what}: row {int(np.argmax(l2))} relL2 = {l2.max():.3e}, row {int(np.argmax(mx))} max = {mx.max():.3e}"
-
-
-def _guarded(sm, count):
-    """a device buffer of [GUARD | count | GUARD] float32: 0x5A, 0xFF, 0x5A; returns (buffer, the payload's address)"""
-    buf = sm.DeviceBuffer((count + 2 * GUARD) * E)
-    assert sm.lib.smfft_memset(buf.ptr, 0x5A, buf.nbytes) == 0
-    if count:
-        assert sm.lib.smfft_memset(buf.ptr + E * GUARD, 0xFF, E * count) == 0
-    return buf, buf.ptr + E * GUARD
-
-
-def _collect(buf, count, finite=True):
-    raw = buf.to_host(np.uint8, ((count + 2 * GUARD) * E,))
-    assert np.all(raw[:E * GUARD] == 0x5A), "the kernel wrote in front of its output"
-    assert np.all(raw[E * (GUARD + count):] == 0x5A), "the kernel wrote past its output"
-    out = raw[E * GUARD:E * (GUARD + count)].view(np.float32).copy()
-    if finite:
-        assert np.all(np.isfinite(out)), "outputs left unwritten"
-    return out
 
 
 def _launch(md, kind, pin, pout, pw, n, batch, grid=None, stream=0):
@@ -132,7 +105,7 @@ def run(sm, md, kind, x, w=None, finite=True, launch=None, in_place=False, grid=
     n = x.shape[1] // 2 if kind.startswith("mdct") else x.shape[1]
     nin, nout = _in_out(kind, n)
     assert x.shape[1] == nin and (w is None or (w.dtype == np.float32 and w.shape == (2 * n,)))
-    dout, pout = _guarded(sm, batch * nout)
+    dout, pout = rh.guarded(sm, batch * nout, E)
     din = dw = None
     try:
         if in_place:
@@ -151,7 +124,7 @@ def run(sm, md, kind, x, w=None, finite=True, launch=None, in_place=False, grid=
         else:
             launch(pin, pout, pw, n, batch)
         assert sm.lib.smfft_synchronize() == 0
-        return _collect(dout, batch * nout, finite).reshape(batch, nout)
+        return rh.collect(dout, batch * nout, np.float32, finite=finite).reshape(batch, nout)
     finally:
         for buf in (din, dout, dw):
             if buf is not None:
@@ -167,7 +140,7 @@ def test_against_fp64(sm, md, n, kind, which):
     past a full tile)"""
     batch = (1, 17, _ffts(n) + 1)[which]
     nin, nout = _in_out(kind, n)
-    x = _rand(np.random.default_rng(10 * n + batch), (batch, nin))
+    x = rh.rand(np.random.default_rng(10 * n + batch), (batch, nin))
     w = _window(kind, n)
     got = run(sm, md, kind, x, w)
     assert got.shape == (batch, nout) and got.dtype == np.float32
@@ -202,7 +175,7 @@ def test_probe_impulses(sm, md, n):
 @pytest.mark.parametrize("n", LENGTHS)
 def test_involution(sm, md, n):
     """dct4(dct4(x)) / (2n) and dst4(dst4(x)) / (2n) return x within twice the row bounds (two launches), batch = 8192 / n + 1"""
-    x = _rand(np.random.default_rng(20 + n), (_ffts(n) + 1, n))
+    x = rh.rand(np.random.default_rng(20 + n), (_ffts(n) + 1, n))
     for kind in ("dct4", "dst4"):
         back = run(sm, md, kind, run(sm, md, kind, x))
         _check_rows(back.astype(np.float64) / (2 * n), x.astype(np.float64), kind, f"n={n} {kind} twice", factor=2.0)
@@ -213,14 +186,14 @@ def _frames(sm, md, flat, w, n, C, F, hop, stride):
     its allocation ends; the (C F, n) coefficients from between guards"""
     flat = np.ascontiguousarray(flat)
     assert flat.dtype == np.float32 and flat.shape == ((C - 1) * stride + (F - 1) * hop + 2 * n,)
-    dout, pout = _guarded(sm, C * F * n)
+    dout, pout = rh.guarded(sm, C * F * n, E)
     din, dw = sm.DeviceBuffer(flat.nbytes), sm.DeviceBuffer(w.nbytes)
     try:
         assert din.nbytes == flat.nbytes and sm.lib.smfft_memcpy_h2d(din.ptr, flat.ctypes.data, flat.nbytes) == 0
         assert sm.lib.smfft_memcpy_h2d(dw.ptr, w.ctypes.data, w.nbytes) == 0
         md.mdct_ptr(din.ptr, pout, dw.ptr, n, C, F, hop, stride)
         assert sm.lib.smfft_synchronize() == 0
-        return _collect(dout, C * F * n).reshape(C * F, n)
+        return rh.collect(dout, C * F * n, np.float32).reshape(C * F, n)
     finally:
         for buf in (din, dout, dw):
             buf.free()
@@ -233,7 +206,7 @@ def test_lapped_transform_reconstructs_the_signal(sm, md, n):
     bounds (two launches) per stretch of N samples.  (The sum is NumPy's here; smfft_amd.mdct.overlap_add is held to it in
     test_tensors_on_the_device.)"""
     C, F = 2, 5
-    s = _rand(np.random.default_rng(25 + n), (C, (F + 1) * n))
+    s = rh.rand(np.random.default_rng(25 + n), (C, (F + 1) * n))
     w = mm.sine_window(n).astype(np.float32)
     X = _frames(sm, md, s.reshape(-1), w, n, C, F, n, (F + 1) * n)
     y = run(sm, md, "imdct", X, w).reshape(C, F, 2 * n)
@@ -250,13 +223,13 @@ def test_frames_from_the_signal_are_the_copied_rows(sm, md, n):
     L = (F + 1) * n
     w = _window("mdct", n)
     for hop, stride in ((n, L), (n, L + 12), (n - 3, L + 5)):
-        flat = _rand(rng, ((C - 1) * stride + (F - 1) * hop + 2 * n,))
+        flat = rh.rand(rng, ((C - 1) * stride + (F - 1) * hop + 2 * n,))
         rows = np.stack([flat[c * stride + f * hop:c * stride + f * hop + 2 * n] for c in range(C) for f in range(F)])
         if (hop, stride) == (n, L):
             assert np.array_equal(rows, mm.frames(flat.reshape(C, L), n).reshape(C * F, 2 * n))
         base = run(sm, md, "mdct", rows, w)
         _check_rows(base, mm.mdct_chain(rows, w), "mdct", f"N={n} copied-out rows, hop {hop}")
-        assert np.array_equal(_bits(_frames(sm, md, flat, w, n, C, F, hop, stride)), _bits(base)), (n, hop, stride)
+        assert np.array_equal(rh.bits(_frames(sm, md, flat, w, n, C, F, hop, stride)), rh.bits(base)), (n, hop, stride)
 
 
 # ---- 3: isolation -------------------------------------------------------------------------------------------------------------------
@@ -268,7 +241,7 @@ def test_probe_rows_are_isolated(sm, md, n):
     batch = 2 * F + 1
     row = F + F // 2
     for kind in ("dct4", "dst4", "mdct", "imdct"):
-        x = _rand(np.random.default_rng(30 + n), (batch, _in_out(kind, n)[0]))
+        x = rh.rand(np.random.default_rng(30 + n), (batch, _in_out(kind, n)[0]))
         w = _window(kind, n)
         clean = run(sm, md, kind, x, w)
         bad = x.copy()
@@ -276,7 +249,7 @@ def test_probe_rows_are_isolated(sm, md, n):
         got = run(sm, md, kind, bad, w, finite=False)
         assert np.isnan(got[row]).all(), (n, kind)
         others = np.arange(batch) != row
-        assert np.array_equal(_bits(got[others]), _bits(clean[others])), (n, kind)
+        assert np.array_equal(rh.bits(got[others]), rh.bits(clean[others])), (n, kind)
 
 
 @pytest.mark.parametrize("n", LENGTHS)
@@ -290,18 +263,18 @@ def test_position_grid_and_in_place_are_invisible(sm, md, n):
     for kind in KINDS:
         rng = np.random.default_rng(40 + n)
         nin = _in_out(kind, n)[0]
-        probe, x, w = _rand(rng, (1, nin)), _rand(rng, (batch, nin)), _window(kind, n)
+        probe, x, w = rh.rand(rng, (1, nin)), rh.rand(rng, (batch, nin)), _window(kind, n)
         x[places] = probe[0]
         alone = run(sm, md, kind, probe, w)
         _check_rows(alone, _want(kind, probe, w), kind, f"n={n} {kind} alone")
         base = run(sm, md, kind, x, w)
         for r in places:
-            assert np.array_equal(_bits(base[r]), _bits(alone[0])), (n, kind, r)
+            assert np.array_equal(rh.bits(base[r]), rh.bits(alone[0])), (n, kind, r)
         for grid in (1, 3):
-            assert np.array_equal(_bits(run(sm, md, kind, x, w, grid=grid)), _bits(base)), (n, kind, grid)
+            assert np.array_equal(rh.bits(run(sm, md, kind, x, w, grid=grid)), rh.bits(base)), (n, kind, grid)
         if kind in ("dct4", "dst4"):
-            assert np.array_equal(_bits(run(sm, md, kind, x, in_place=True)), _bits(base)), (n, kind, "in place")
-            assert np.array_equal(_bits(run(sm, md, kind, x, in_place=True, grid=1)), _bits(base)), (n, kind, "in place, one workgroup")
+            assert np.array_equal(rh.bits(run(sm, md, kind, x, in_place=True)), rh.bits(base)), (n, kind, "in place")
+            assert np.array_equal(rh.bits(run(sm, md, kind, x, in_place=True, grid=1)), rh.bits(base)), (n, kind, "in place, one workgroup")
 
 
 # ---- 4: the grid-stride loop ----------------------------------------------------------------------------------------------------------
@@ -309,11 +282,11 @@ def test_position_grid_and_in_place_are_invisible(sm, md, n):
 def test_grid_stride_loop(sm, md, kind):
     """n = 512, batch = 100 on grid = 2: seven tiles of sixteen rows, the last one ragged, three or four per workgroup"""
     n, batch = 512, 100
-    x = _rand(np.random.default_rng(50), (batch, _in_out(kind, n)[0]))
+    x = rh.rand(np.random.default_rng(50), (batch, _in_out(kind, n)[0]))
     w = _window(kind, n)
     got = run(sm, md, kind, x, w, grid=2)
     _check_rows(got, _want(kind, x, w), kind, f"grid-stride n={n} batch={batch} {kind}")
-    assert np.array_equal(_bits(got), _bits(run(sm, md, kind, x, w)))
+    assert np.array_equal(rh.bits(got), rh.bits(run(sm, md, kind, x, w)))
 
 
 # ---- 5: bounds ------------------------------------------------------------------------------------------------------------------------
@@ -325,7 +298,7 @@ def test_bounds(sm, md, n, batch):
     NaN, and show in the result.)"""
     for kind in KINDS:
         nin, nout = _in_out(kind, n)
-        x = _rand(np.random.default_rng(60 + n), (batch, nin))
+        x = rh.rand(np.random.default_rng(60 + n), (batch, nin))
         w = _window(kind, n)
         base = run(sm, md, kind, x, w)
         _check_rows(base, _want(kind, x, w), kind, f"n={n} batch={batch} {kind}")
@@ -339,7 +312,7 @@ def test_bounds(sm, md, n, batch):
             if rw is not None:
                 rw.outside_unchanged(whole=True)
             got = rout.outside_unchanged(whole=False).view(np.float32).reshape(batch, nout)
-            assert np.array_equal(_bits(got), _bits(base)), (n, batch, kind)
+            assert np.array_equal(rh.bits(got), rh.bits(base)), (n, batch, kind)
         finally:
             for r in (rin, rout, rw):
                 if r is not None:
@@ -356,7 +329,7 @@ def test_offsets_beyond_two_to_the_31(sm, md):
     assert (batch - 8) * n == 1 << 31
     rows = [0, 1, (1 << 29) // n - 1, (1 << 29) // n, (1 << 30) // n - 1, (1 << 30) // n, (1 << 31) // n - 1, (1 << 31) // n, batch - 2, batch - 1]
     zeros = [2, (1 << 29) // n + 1, (1 << 31) // n - 2, (1 << 31) // n + 1, batch - 3]
-    x = _rand(np.random.default_rng(70), (len(rows), n))
+    x = rh.rand(np.random.default_rng(70), (len(rows), n))
     want = mm.chain(x)
     buf = sm.DeviceBuffer((batch * n + GUARD) * E)
     try:
@@ -392,7 +365,7 @@ def test_caller_stream(sm, md):
     assert hip.hipStreamCreate(ctypes.byref(stream)) == 0 and stream.value
     rng = np.random.default_rng(11)
     for n, kind in ((1024, "dst4"), (4096, "mdct"), (2048, "imdct")):
-        x = _rand(rng, (37, _in_out(kind, n)[0]))
+        x = rh.rand(rng, (37, _in_out(kind, n)[0]))
         w = _window(kind, n)
 
         def launch(pin, pout, pw, nn, batch):
@@ -410,7 +383,7 @@ def test_benchmark_forms_add_to_the_timer(sm, md):
     rng = np.random.default_rng(12)
     total = ctypes.c_double(1.0)
     for kind in ("dct4", "mdct", "imdct"):
-        x = _rand(rng, (300, _in_out(kind, n)[0]))
+        x = rh.rand(rng, (300, _in_out(kind, n)[0]))
         w = _window(kind, n)
         base = run(sm, md, kind, x, w)
         _check_rows(base, _want(kind, x, w), kind, f"benchmark form {kind}")
@@ -434,7 +407,7 @@ def test_benchmark_forms_add_to_the_timer(sm, md):
                 status, ms = md.imdct_benchmark(pin, pout, pw, nn, batch)
             assert status == 0 and ms > 0.0
         for form in (c_form, mirror):
-            assert np.array_equal(_bits(run(sm, md, kind, x, w, launch=form)), _bits(base)), (kind, form.__name__)
+            assert np.array_equal(rh.bits(run(sm, md, kind, x, w, launch=form)), rh.bits(base)), (kind, form.__name__)
 
 
 _TENSOR_SCRIPT = r"""

@@ -3,7 +3,6 @@
 that reference and in fp32 stays far inside the GPU tests' bounds; the model's and the library's fft_size agree over the whole grid; the
 gfx950 code of the five kernels keeps the budget of the FIR bank's and the chirp-z kernels; and the C ABI declares, exports and
 validates the four entry points without a device.  No GPU code is run (hipcc cross-compiles gfx950)."""
-import concurrent.futures
 import os
 import re
 import subprocess
@@ -139,23 +138,12 @@ sys.exit(0 if bad == [-1] * len(bad) and f(300, 200) == 512 and f(4096, 1) == 40
 
 
 # ---- 2: ISA budget and inventory -------------------------------------------------------------------------------
-def _occupancy(vgprs):
-    """waves per SIMD that the vector registers allow: 512 registers in granules of 8"""
-    return 512 // (-(-vgprs // 8) * 8)
-
-
 @pytest.fixture(scope="module")
 def isa(tmp_path_factory):
     """{M: assembly of smfft_rowconv_<M>.o as the Makefile compiles it}"""
     if not os.path.exists(ac.HIPCC):
         pytest.skip("hipcc not installed")
-    tmp = tmp_path_factory.mktemp("rowconv_isa")
-
-    def compile_one(m):
-        return ac.device_asm(os.path.join(CSRC, "smfft_rowconv.hip"), ["-I" + CSRC] + ac.makefile_flags("ROWCONV", m) + [f"-DSMFFT_ROWCONV_N={m}"],
-                             tmp / f"smfft_rowconv_{m}.s")
-    with concurrent.futures.ThreadPoolExecutor(5) as pool:
-        return dict(zip(SIZES, pool.map(compile_one, SIZES)))
+    return ac.addon_isa("smfft_rowconv", "ROWCONV", SIZES, tmp_path_factory.mktemp("rowconv_isa"))
 
 
 def test_isa_budget_of_what_ships(isa):
@@ -177,9 +165,9 @@ def test_isa_budget_of_what_ships(isa):
         assert not [line for line in body if re.match(r"v_pk_(add|mul|fma)_f32", line)], name
         assert ac.descriptor_field(descs, name, "private_segment_fixed_size") == 0, name
         v, lds = ac.descriptor_field(descs, name, "next_free_vgpr"), ac.descriptor_field(descs, name, "group_segment_fixed_size")
-        print(f"M={m}: rowconv_kernel {v} VGPRs ({_occupancy(v)} waves per SIMD), {lds} B of LDS, 0 B of scratch")
+        print(f"M={m}: rowconv_kernel {v} VGPRs ({ac.occupancy(v)} waves per SIMD), {lds} B of LDS, 0 B of scratch")
         assert lds <= LDS_BUDGET and 2 * lds <= ac.LDS_PER_CU, (name, lds)
-        assert v <= 256 and _occupancy(v) >= 2, (name, v)
+        assert v <= 256 and ac.occupancy(v) >= 2, (name, v)
         loads = [i for i, line in enumerate(body) if line.startswith("global_load") and re.search(r"\bnt\b", line)]
         assert len(loads) == 32 and all(re.match(r"global_load_dwordx2\s", body[i]) for i in loads), (name, len(loads))
         between = body[loads[0]:loads[-1] + 1]
@@ -200,11 +188,7 @@ def test_library_ships_five_kernels_and_the_inventory_names_them(rowconv_lib):
 def test_isa_identity_compares_the_library():
     """tools/isa_identity.py compiles the five objects with the Makefile's flags and -I., like the other add-ons' (the tool itself
     needs the history of a git checkout and minutes of compiling: it is run by hand, DESIGN.md section 20 has its verdict)"""
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import isa_identity
-    assert ("smfft_rowconv", "ROWCONV", SIZES, True) in isa_identity.ADDONS
-    names = [u[0] for u in isa_identity.units(ROOT)]
-    assert all(f"smfft_rowconv_{m}" in names for m in SIZES) and len(names) == len(set(names))
+    ac.check_isa_identity_lists("smfft_rowconv", "ROWCONV", SIZES)
 
 
 # ---- 3: declarations and exports ---------------------------------------------------------------------------------
@@ -235,8 +219,7 @@ def test_python_mirror_matches_header(rowconv_lib):
 
 
 def test_library_exports_exactly_the_four_symbols(rowconv_lib):
-    nm = subprocess.run(["nm", "-D", "--defined-only", rowconv_lib], capture_output=True, text=True, check=True).stdout
-    assert sorted(re.findall(r" T (smfft_\w+)$", nm, re.M)) == sorted(NAMES)
+    ac.check_exports(rowconv_lib, NAMES)
 
 
 # ---- 4: rejections -------------------------------------------------------------------------------------------------
@@ -329,7 +312,4 @@ def test_python_wrappers_refuse_before_a_device(rowconv_lib):
 
 
 def test_import_does_not_load_the_library():
-    code = ("import sys; sys.path.insert(0, sys.argv[1]); import smfft_amd, smfft_amd.rowconv as l; assert l._lib is None; "
-            "maps = open('/proc/self/maps').read(); assert 'libsmfft_rowconv' not in maps; print('ok')")
-    p = subprocess.run([sys.executable, "-c", code, ROOT], capture_output=True, text=True, timeout=120)
-    assert p.returncode == 0 and "ok" in p.stdout, p.stdout + p.stderr
+    ac.check_import_does_not_load("rowconv", "smfft_rowconv")

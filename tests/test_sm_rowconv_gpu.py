@@ -26,6 +26,7 @@ import sys
 import numpy as np
 import pytest
 
+from tests import rows_gpu_harness as rh
 from tests.fir_gpu_harness import GRID_CAP, GUARD, ROW_MAX, ROW_REL_L2
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
@@ -36,7 +37,7 @@ pytestmark = pytest.mark.gpu
 SIZES = [256, 512, 1024, 2048, 4096]
 LARGEST = {256: (128, 129), 512: (256, 257), 1024: (512, 513), 2048: (1024, 1025), 4096: (2048, 2049)}      # n_a + n_b - 1 = M
 MODES = (False, True)       # correlate
-WORST = {}                  # M -> [relL2, max / max]: the worst figures measured in this run
+WORST = rh.Worst()      # M -> [relL2, max / max]: the worst figures measured in this run
 
 
 @pytest.fixture(scope="module")
@@ -53,14 +54,6 @@ def rc():
     return rowconv
 
 
-def _rand(rng, shape):
-    return (rng.standard_normal(shape) + 1j * rng.standard_normal(shape)).astype(np.complex64)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
 def _mode(correlate):
     return "correlate" if correlate else "convolve"
 
@@ -70,31 +63,9 @@ def _check_rows(got, want, M, what):
     d = got.astype(np.complex128) - want
     l2 = np.linalg.norm(d, axis=1) / np.maximum(np.linalg.norm(want, axis=1), 1e-30)
     mx = np.max(np.abs(d), axis=1) / np.maximum(np.max(np.abs(want), axis=1), 1e-30)
-    worst = WORST.setdefault(M, [0.0, 0.0])
-    worst[0], worst[1] = max(worst[0], float(l2.max())), max(worst[1], float(mx.max()))
+    worst = WORST.record(M, l2, mx)
     print(f"{what}: worst row relL2 = {l2.max():.3e}, max |d| / max |want| = {mx.max():.3e}  (M = {M} so far: {worst[0]:.3e}, {worst[1]:.3e})")
     assert l2.max() <= ROW_REL_L2 and mx.max() <= ROW_MAX, f"{what}: row {int(np.argmax(l2))} relL2 = {l2.max():.3e}, row {int(np.argmax(mx))} max = {mx.max():.3e}"
-
-
-def _guarded(sm, count, front=0):
-    """a device buffer of [GUARD + front | count | GUARD] float2: 0x5A, 0xFF, 0x5A; returns (buffer, the payload's address)"""
-    front += GUARD
-    buf = sm.DeviceBuffer((front + count + GUARD) * 8)
-    assert sm.lib.smfft_memset(buf.ptr, 0x5A, buf.nbytes) == 0
-    if count:
-        assert sm.lib.smfft_memset(buf.ptr + 8 * front, 0xFF, 8 * count) == 0
-    return buf, buf.ptr + 8 * front
-
-
-def _collect(buf, count, front=0, finite=True):
-    front += GUARD
-    raw = buf.to_host(np.uint8, ((front + count + GUARD) * 8,))
-    assert np.all(raw[:8 * front] == 0x5A), "the kernel wrote in front of its output"
-    assert np.all(raw[8 * (front + count):] == 0x5A), "the kernel wrote past its output"
-    out = raw[8 * front:8 * (front + count)].view(np.complex64).copy()
-    if finite:
-        assert np.all(np.isfinite(out.view(np.float32))), "outputs left unwritten"
-    return out
 
 
 def run(sm, rc, a, b, correlate, first=0, m=None, front=0, finite=True, launch=None):
@@ -118,14 +89,14 @@ def run(sm, rc, a, b, correlate, first=0, m=None, front=0, finite=True, launch=N
         assert db.nbytes == b.nbytes
         pb = db.ptr
     first, m = rm.window(n_a, n_b, first, m)
-    dout, pout = _guarded(sm, batch * m, front)
+    dout, pout = rh.guarded(sm, batch * m, 8, front)
     try:
         if launch is None:
             rc.launch(da.ptr, pb, pout, n_a, n_b, first, m, batch, correlate)
         else:
             launch(da.ptr, pb, pout, n_a, n_b, first, m, batch, correlate)
         assert sm.lib.smfft_synchronize() == 0
-        return _collect(dout, batch * m, front, finite).reshape(batch, m)
+        return rh.collect(dout, batch * m, np.complex64, front, finite).reshape(batch, m)
     finally:
         for buf in (da, db, dout):
             if buf is not None:
@@ -151,7 +122,7 @@ def test_against_fp64(sm, rc, n_a, n_b):
     """batch = 2F + 1 (two full tiles and one row), the full output, both modes"""
     rng = np.random.default_rng(1000 * n_a + n_b)
     batch = _batch(n_a, n_b)
-    a, b = _rand(rng, (batch, n_a)), _rand(rng, (batch, n_b))
+    a, b = rh.rand(rng, (batch, n_a), np.complex64), rh.rand(rng, (batch, n_b), np.complex64)
     for correlate in MODES:
         got = run(sm, rc, a, b, correlate)
         assert got.shape == (batch, n_a + n_b - 1)
@@ -168,7 +139,7 @@ def test_probe_impulses(sm, rc, n_a, n_b):
     rng = np.random.default_rng(40 + n_a)
     a = np.zeros((len(js), n_a), np.complex64)
     a[np.arange(len(js)), js] = 1
-    b = _rand(rng, (len(js), n_b))
+    b = rh.rand(rng, (len(js), n_b), np.complex64)
     for correlate in MODES:
         got = run(sm, rc, a, b, correlate).astype(np.complex128)
         second = rm.second_operand(b.astype(np.complex128), correlate)
@@ -185,7 +156,7 @@ def test_probe_autocorrelation(sm, rc, n):
     """d_a == d_b with correlate set, batch = 2F + 1: the fp64 autocorrelation within the row bounds; lag 0, at index n - 1, is ||a||^2
     within ROW_MAX ||a||^2; and the bits are those of two buffers with the same content"""
     rng = np.random.default_rng(45 + n)
-    a = _rand(rng, (_batch(n, n), n))
+    a = rh.rand(rng, (_batch(n, n), n), np.complex64)
     got = run(sm, rc, a, None, True)
     assert got.shape == (a.shape[0], 2 * n - 1)
     _check_rows(got, rm.direct(a, a, True), rm.fft_size(n, n), f"autocorrelation n={n}")
@@ -193,7 +164,7 @@ def test_probe_autocorrelation(sm, rc, n):
     err = np.abs(got[:, n - 1].astype(np.complex128) - energy) / energy
     print(f"autocorrelation n={n}: worst |y[n - 1] - ||a||^2| / ||a||^2 = {err.max():.3e}")
     assert err.max() <= ROW_MAX, (n, err.max())
-    assert np.array_equal(_bits(got), _bits(run(sm, rc, a, a.copy(), True))), n
+    assert np.array_equal(rh.bits(got), rh.bits(run(sm, rc, a, a.copy(), True))), n
 
 
 # ---- 3: the window ------------------------------------------------------------------------------------------------------------------
@@ -206,14 +177,14 @@ def test_window(sm, rc, n_a, n_b):
     assert (len(windows) == 3) == ((n_a, n_b) == (1, 4096))
     rng = np.random.default_rng(55 + n_a)
     batch = _batch(n_a, n_b)
-    a, b = _rand(rng, (batch, n_a)), _rand(rng, (batch, n_b))
+    a, b = rh.rand(rng, (batch, n_a), np.complex64), rh.rand(rng, (batch, n_b), np.complex64)
     for correlate in MODES:
         base = run(sm, rc, a, b, correlate)
         _check_rows(base, rm.direct(a, b, correlate), rm.fft_size(n_a, n_b), f"n_a={n_a} n_b={n_b} {_mode(correlate)} full")
         for first, m in windows:
             got = run(sm, rc, a, b, correlate, first=first, m=m)
             assert got.shape == (batch, m)
-            assert np.array_equal(_bits(got), _bits(base[:, first:first + m])), (n_a, n_b, correlate, first, m)
+            assert np.array_equal(rh.bits(got), rh.bits(base[:, first:first + m])), (n_a, n_b, correlate, first, m)
 
 
 # ---- 4: isolation -------------------------------------------------------------------------------------------------------------------
@@ -223,7 +194,7 @@ def test_probe_rows_are_isolated(sm, rc, n_a, n_b):
     poisoned row is NaN in all its outputs, the zero row's are +0 bits, and every other row keeps the bits of the clean run"""
     F = _ffts(n_a, n_b)
     rng = np.random.default_rng(50 + n_a)
-    a, b = _rand(rng, (3 * F, n_a)), _rand(rng, (3 * F, n_b))
+    a, b = rh.rand(rng, (3 * F, n_a), np.complex64), rh.rand(rng, (3 * F, n_b), np.complex64)
     whole, single, zero = F + F // 2, 2 * F + F // 3, F // 5
     assert len({whole, single, zero}) == 3
     for correlate in MODES:
@@ -240,13 +211,13 @@ def test_probe_rows_are_isolated(sm, rc, n_a, n_b):
             got = run(sm, rc, bad_a, bad_b, correlate, finite=False)
             assert got.shape == clean.shape
             if case == "a all zero":
-                words = _bits(got[row])
+                words = rh.bits(got[row])
                 print(f"n_a={n_a} n_b={n_b} {_mode(correlate)} zero row: {int(np.count_nonzero(words))} words that are not +0")
                 assert not words.any(), (n_a, n_b, correlate, "a zero row is not +0 everywhere")
             else:
                 assert np.isnan(got[row]).all(), (n_a, n_b, correlate, case, int(np.isnan(got[row]).sum()))
             others = np.arange(3 * F) != row
-            assert np.array_equal(_bits(got[others]), _bits(clean[others])), (n_a, n_b, correlate, case)
+            assert np.array_equal(rh.bits(got[others]), rh.bits(clean[others])), (n_a, n_b, correlate, case)
 
 
 # ---- 5: the grid --------------------------------------------------------------------------------------------------------------------
@@ -258,13 +229,13 @@ def test_grid_is_invisible(sm, rc, M):
     assert rm.fft_size(n_a, n_b) == M and n_a + n_b - 1 == M
     rng = np.random.default_rng(60 + M)
     batch = _batch(n_a, n_b, 5)
-    a, b = _rand(rng, (batch, n_a)), _rand(rng, (batch, n_b))
+    a, b = rh.rand(rng, (batch, n_a), np.complex64), rh.rand(rng, (batch, n_b), np.complex64)
     for correlate in MODES:
         base = run(sm, rc, a, b, correlate)
         _check_rows(base, rm.direct(a, b, correlate), M, f"M={M} n_a={n_a} n_b={n_b} {_mode(correlate)} six tiles")
         for grid in (1, 2, 3, 6, 12288):
             got = run(sm, rc, a, b, correlate, launch=lambda da, db, dout, na, nb, first, m, bt, c: rc.launch_tuned(da, db, dout, na, nb, first, m, bt, grid, c))
-            assert np.array_equal(_bits(got), _bits(base)), (M, correlate, grid)
+            assert np.array_equal(rh.bits(got), rh.bits(base)), (M, correlate, grid)
 
 
 @pytest.mark.parametrize("n_a, n_b, batch, correlate", [(5, 3, 16 * (2 * 12288) + 7, False), (1025, 1024, 2 * 12288 + 1, True)])
@@ -277,7 +248,7 @@ def test_grid_stride_loop(sm, rc, n_a, n_b, batch, correlate):
     F = _ffts(n_a, n_b)
     assert GRID_CAP == 12288 and GRID_CAP < -(-batch // F) <= 3 * GRID_CAP and batch % F
     rng = np.random.default_rng(12288 + n_a)
-    a, b = _rand(rng, (batch, n_a)), _rand(rng, (batch, n_b))
+    a, b = rh.rand(rng, (batch, n_a), np.complex64), rh.rand(rng, (batch, n_b), np.complex64)
     got = run(sm, rc, a, b, correlate)
     M = rm.fft_size(n_a, n_b)
     what = f"grid-stride n_a={n_a} n_b={n_b} batch={batch} {_mode(correlate)}"
@@ -298,14 +269,14 @@ def test_bounds(sm, rc, n_a, n_b, correlate):
     F = _ffts(n_a, n_b)
     rng = np.random.default_rng(70 + n_a)
     for batch in sorted({1, F + 1} | ({F - 1} if F > 1 else set())):
-        a, b = _rand(rng, (batch, n_a)), _rand(rng, (batch, n_b))
+        a, b = rh.rand(rng, (batch, n_a), np.complex64), rh.rand(rng, (batch, n_b), np.complex64)
         base = run(sm, rc, a, b, correlate)
         _check_rows(base, rm.direct(a, b, correlate), rm.fft_size(n_a, n_b), f"n_a={n_a} n_b={n_b} batch={batch}")
         for front in (1, 3):
             got = run(sm, rc, a, b, correlate, front=front)
-            assert np.array_equal(_bits(got), _bits(base)), f"n_a={n_a} n_b={n_b} batch={batch} front={front}: the result depends on placement"
+            assert np.array_equal(rh.bits(got), rh.bits(base)), f"n_a={n_a} n_b={n_b} batch={batch} front={front}: the result depends on placement"
             window = run(sm, rc, a, b, correlate, first=n_b - 1, m=1, front=front)            # lag 0 alone, at an odd base
-            assert np.array_equal(_bits(window), _bits(base[:, n_b - 1:n_b])), (n_a, n_b, batch, front)
+            assert np.array_equal(rh.bits(window), rh.bits(base[:, n_b - 1:n_b])), (n_a, n_b, batch, front)
 
 
 # ---- 7: 64-bit offsets ----------------------------------------------------------------------------------------------------------------
@@ -325,13 +296,13 @@ def test_offsets_beyond_two_to_the_31(sm, rc, n_a, n_b, first, m, correlate):
     zeros = [1, straddle // 2, straddle - 1, straddle + 1, batch - 3]
     full = n_a + n_b - 1
     rng = np.random.default_rng(31 + n_a)
-    a, b = _rand(rng, (len(rows), n_a)), _rand(rng, (len(rows), n_b))
+    a, b = rh.rand(rng, (len(rows), n_a), np.complex64), rh.rand(rng, (len(rows), n_b), np.complex64)
     want_full = rm.direct(a, b, correlate)
     while m < full:       # (m = 1: a pair whose one output is below half its expectation is drawn again)
         small = np.linalg.norm(want_full[:, first:first + m], axis=1) < 0.5 * np.sqrt(m / full) * np.linalg.norm(want_full, axis=1)
         if not small.any():
             break
-        a[small], b[small] = _rand(rng, (int(small.sum()), n_a)), _rand(rng, (int(small.sum()), n_b))
+        a[small], b[small] = rh.rand(rng, (int(small.sum()), n_a), np.complex64), rh.rand(rng, (int(small.sum()), n_b), np.complex64)
         want_full = rm.direct(a, b, correlate)
     want = want_full[:, first:first + m]
     da, db = sm.DeviceBuffer(batch * n_a * 8), sm.DeviceBuffer(batch * n_b * 8)
@@ -356,14 +327,14 @@ def test_offsets_beyond_two_to_the_31(sm, rc, n_a, n_b, first, m, correlate):
         if m == 1:
             whole = np.empty(batch, np.complex64)
             assert sm.lib.smfft_memcpy_d2h(whole.ctypes.data, dout.ptr, whole.nbytes) == 0
-            words = _bits(np.delete(whole, rows))
+            words = rh.bits(np.delete(whole, rows))
             print(f"{words.size // 2} zero rows: {int(np.count_nonzero(words))} words that are not +0")
             assert not words.any(), "a zero row is not +0"
         else:
             for r in zeros:
                 row = np.empty(m, np.complex64)
                 assert sm.lib.smfft_memcpy_d2h(row.ctypes.data, dout.ptr + r * m * 8, m * 8) == 0
-                words = _bits(row)
+                words = rh.bits(row)
                 print(f"zero row {r}: {int(np.count_nonzero(words))} words that are not +0 ({int(np.count_nonzero(words == 0x80000000))} of them -0)")
                 assert not words.any(), f"zero row {r} is not +0 everywhere"
     finally:
@@ -382,7 +353,7 @@ def test_caller_stream(sm, rc):
     assert hip.hipStreamCreate(ctypes.byref(stream)) == 0 and stream.value
     rng = np.random.default_rng(11)
     for n_a, n_b, correlate in ((1000, 25, True), (100, 300, False)):
-        a, b = _rand(rng, (37, n_a)), _rand(rng, (37, n_b))
+        a, b = rh.rand(rng, (37, n_a), np.complex64), rh.rand(rng, (37, n_b), np.complex64)
 
         def launch(da, db, dout, na, nb, first, m, batch, c):
             assert sm.lib.smfft_synchronize() == 0                              # the prefill of the output, on the null stream
@@ -396,7 +367,7 @@ def test_benchmark_form_adds_to_the_timer(sm, rc):
     """the library's smfft_rowconv_benchmark adds its milliseconds to a non-zero total and fills the output; so does the mirror's"""
     n_a, n_b = 1536, 513
     rng = np.random.default_rng(12)
-    a, b = _rand(rng, (300, n_a)), _rand(rng, (300, n_b))
+    a, b = rh.rand(rng, (300, n_a), np.complex64), rh.rand(rng, (300, n_b), np.complex64)
     total = ctypes.c_double(1.0)
 
     def c_form(da, db, dout, na, nb, first, m, batch, c):
@@ -408,7 +379,7 @@ def test_benchmark_form_adds_to_the_timer(sm, rc):
     def mirror(da, db, dout, na, nb, first, m, batch, c):
         status, ms = rc.benchmark(da, db, dout, na, nb, first, m, batch, c)
         assert status == 0 and ms > 0.0
-    assert np.array_equal(_bits(run(sm, rc, a, b, True, launch=mirror)), _bits(out))
+    assert np.array_equal(rh.bits(run(sm, rc, a, b, True, launch=mirror)), rh.bits(out))
 
 
 def test_host_round_trip(sm, rc):
@@ -420,24 +391,24 @@ def test_host_round_trip(sm, rc):
     a32, b32 = a1.astype(np.complex64), b1.astype(np.complex64)
     got = rc.convolve(a1, b1)
     assert got.shape == (1024,) and got.dtype == np.complex64
-    assert np.array_equal(_bits(got), _bits(run(sm, rc, a32[None], b32[None], False)[0]))
+    assert np.array_equal(rh.bits(got), rh.bits(run(sm, rc, a32[None], b32[None], False)[0]))
     _check_rows(got[None], np.convolve(a32.astype(np.complex128), b32.astype(np.complex128))[None], 1024, "convolve() 1-D against np.convolve")
     got = rc.convolve(a1, b1, correlate=True)
     _check_rows(got[None], np.correlate(a32.astype(np.complex128), b32.astype(np.complex128), "full")[None], 1024, "convolve() 1-D against np.correlate")
     lags = rc.convolve(a1, b1, correlate=True, first=25 - 1 - 16, m=33)              # the lags -16 ... 16
-    assert lags.shape == (33,) and np.array_equal(_bits(lags), _bits(got[8:41]))
+    assert lags.shape == (33,) and np.array_equal(rh.bits(lags), rh.bits(got[8:41]))
     tail = rc.convolve(a1, b1, first=1000)
-    assert tail.shape == (24,) and np.array_equal(_bits(tail), _bits(rc.convolve(a1, b1)[1000:]))
-    a3, b3 = _rand(rng, (2, 3, 257)), _rand(rng, (2, 3, 100))
+    assert tail.shape == (24,) and np.array_equal(rh.bits(tail), rh.bits(rc.convolve(a1, b1)[1000:]))
+    a3, b3 = rh.rand(rng, (2, 3, 257), np.complex64), rh.rand(rng, (2, 3, 100), np.complex64)
     got = rc.convolve(a3, b3, correlate=True)
     assert got.shape == (2, 3, 356) and got.dtype == np.complex64
-    assert np.array_equal(_bits(got.reshape(6, 356)), _bits(run(sm, rc, a3.reshape(6, 257), b3.reshape(6, 100), True)))
+    assert np.array_equal(rh.bits(got.reshape(6, 356)), rh.bits(run(sm, rc, a3.reshape(6, 257), b3.reshape(6, 100), True)))
     ar, br = rng.standard_normal((4, 129)), rng.standard_normal((4, 130))            # real float64
     got = rc.convolve(ar, br)
     want = np.stack([np.convolve(ar[r].astype(np.float32).astype(np.float64), br[r].astype(np.float32).astype(np.float64)) for r in range(4)])
     _check_rows(got, want.astype(np.complex128), 512, "convolve() real")
     assert got.dtype == np.complex64 and got.shape == (4, 258)
-    assert np.array_equal(_bits(rc.convolve(ar.astype(np.float32), br.astype(np.float32))), _bits(got))
+    assert np.array_equal(rh.bits(rc.convolve(ar.astype(np.float32), br.astype(np.float32))), rh.bits(got))
     empty = rc.convolve(np.zeros((0, 5), np.complex64), np.zeros((0, 3), np.complex64))
     assert empty.shape == (0, 7) and empty.dtype == np.complex64
     assert ROW_REL_L2 == 1e-6 and ROW_MAX == 5e-6

@@ -4,7 +4,6 @@ inside the GPU tests' bounds at every shape and scale, while without it it does 
 (smfft_rowconv_real_scale.hpp), compiled alone under the address and undefined-behaviour sanitizers, is the model's; the gfx950 code
 of the five kernels keeps its budget; and the C ABI declares, exports and validates the four entry points without a device.  No GPU
 code is run (hipcc cross-compiles gfx950)."""
-import concurrent.futures
 import os
 import re
 import shutil
@@ -188,23 +187,12 @@ def test_scaling_rule_is_the_models_and_clean_under_asan_and_ubsan(tmp_path):
 
 
 # ---- 3: ISA budget and inventory -------------------------------------------------------------------------------
-def _occupancy(vgprs):
-    """waves per SIMD that the vector registers allow: 512 registers in granules of 8"""
-    return 512 // (-(-vgprs // 8) * 8)
-
-
 @pytest.fixture(scope="module")
 def isa(tmp_path_factory):
     """{M: assembly of smfft_rowconv_real_<M>.o as the Makefile compiles it}"""
     if not os.path.exists(ac.HIPCC):
         pytest.skip("hipcc not installed")
-    tmp = tmp_path_factory.mktemp("rowconv_real_isa")
-
-    def compile_one(m):
-        return ac.device_asm(os.path.join(CSRC, "smfft_rowconv_real.hip"), ["-I" + CSRC] + ac.makefile_flags("ROWCONV_REAL", m) + [f"-DSMFFT_ROWCONV_REAL_N={m}"],
-                             tmp / f"smfft_rowconv_real_{m}.s")
-    with concurrent.futures.ThreadPoolExecutor(5) as pool:
-        return dict(zip(SIZES, pool.map(compile_one, SIZES)))
+    return ac.addon_isa("smfft_rowconv_real", "ROWCONV_REAL", SIZES, tmp_path_factory.mktemp("rowconv_real_isa"))
 
 
 def test_isa_budget_of_what_ships(isa):
@@ -225,9 +213,9 @@ def test_isa_budget_of_what_ships(isa):
         assert not [line for line in body if re.match(r"v_pk_(add|mul|fma)_f32", line)], name
         assert ac.descriptor_field(descs, name, "private_segment_fixed_size") == 0, name
         v, lds = ac.descriptor_field(descs, name, "next_free_vgpr"), ac.descriptor_field(descs, name, "group_segment_fixed_size")
-        print(f"M={m}: rowconv_real_kernel {v} VGPRs ({_occupancy(v)} waves per SIMD), {lds} B of LDS, 0 B of scratch")
+        print(f"M={m}: rowconv_real_kernel {v} VGPRs ({ac.occupancy(v)} waves per SIMD), {lds} B of LDS, 0 B of scratch")
         assert LDS_BUDGET <= lds <= LDS_BUDGET + LDS_REDUCTION and 2 * lds <= ac.LDS_PER_CU, (name, lds)
-        assert v <= 256 and _occupancy(v) >= 2, (name, v)
+        assert v <= 256 and ac.occupancy(v) >= 2, (name, v)
         loads = [i for i, line in enumerate(body) if line.startswith("global_load") and re.search(r"\bnt\b", line)]      # (the others: twiddles)
         assert len(loads) == 32 and all(re.match(r"global_load_dword\s", body[i]) for i in loads), (name, len(loads))
         between = body[loads[0]:loads[-1] + 1]
@@ -246,10 +234,7 @@ def test_library_ships_five_kernels_and_the_inventory_names_them(real_lib):
 def test_isa_identity_compares_the_library():
     """tools/isa_identity.py compiles the five objects with the Makefile's flags and -I., like the other add-ons' (the tool itself
     needs the history of a git checkout and minutes of compiling: it is run by hand, DESIGN.md section 21 has its verdict)"""
-    import isa_identity
-    assert ("smfft_rowconv_real", "ROWCONV_REAL", SIZES, True) in isa_identity.ADDONS
-    names = [u[0] for u in isa_identity.units(ROOT)]
-    assert all(f"smfft_rowconv_real_{m}" in names for m in SIZES) and len(names) == len(set(names))
+    ac.check_isa_identity_lists("smfft_rowconv_real", "ROWCONV_REAL", SIZES)
 
 
 # ---- 4: declarations and exports ---------------------------------------------------------------------------------
@@ -281,8 +266,7 @@ def test_python_mirror_matches_header(real_lib):
 
 
 def test_library_exports_exactly_the_four_symbols(real_lib):
-    nm = subprocess.run(["nm", "-D", "--defined-only", real_lib], capture_output=True, text=True, check=True).stdout
-    assert sorted(re.findall(r" T (smfft_\w+)$", nm, re.M)) == sorted(NAMES)
+    ac.check_exports(real_lib, NAMES)
 
 
 # ---- 5: rejections -------------------------------------------------------------------------------------------------
@@ -379,7 +363,4 @@ def test_python_wrappers_refuse_before_a_device(real_lib):
 
 
 def test_import_does_not_load_the_library():
-    code = ("import sys; sys.path.insert(0, sys.argv[1]); import smfft_amd, smfft_amd.rowconv_real as l; assert l._lib is None; "
-            "maps = open('/proc/self/maps').read(); assert 'libsmfft_rowconv_real' not in maps; print('ok')")
-    p = subprocess.run([sys.executable, "-c", code, ROOT], capture_output=True, text=True, timeout=120)
-    assert p.returncode == 0 and "ok" in p.stdout, p.stdout + p.stderr
+    ac.check_import_does_not_load("rowconv_real", "smfft_rowconv_real")

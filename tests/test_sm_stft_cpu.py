@@ -3,7 +3,6 @@ the fp64 sum of the definition, np.fft.rfft / irfft and torch.stft / torch.istft
 to 1.5 and reconstructs the signal, and in fp32 the chain stays inside the GPU tests' bounds; the gfx950 code of the fifteen kernels
 keeps its budget; and the C ABI declares, exports and validates the eight entry points without a device.  No GPU code is run (hipcc
 cross-compiles gfx950)."""
-import concurrent.futures
 import os
 import re
 import subprocess
@@ -153,36 +152,26 @@ def test_fp32_model_is_inside_the_bounds():
 def test_source_builds_its_twiddles_from_the_dct_table():
     """W_n^k comes from the fp64-rounded octant of smfft_twiddles_dct.inc through the Rows<M> construction: no table of its own and
     nothing transcendental in the source"""
-    source = open(os.path.join(CSRC, "smfft_stft.hip")).read()
-    assert "smfft/smfft_twiddles_dct.inc" in source and source.count(".inc\"") == 1
+    # the table lives in the header that the four half-length row libraries share, which includes it exactly once
+    source, shared = open(os.path.join(CSRC, "smfft_stft.hip")).read(), open(os.path.join(CSRC, "smfft_rows.hpp")).read()
+    assert '#include "smfft/smfft_twiddles_dct.inc"' in shared and shared.count(".inc\"") == 1
+    assert '#include "smfft_rows.hpp"' in source and not re.search(r'#include "[^"]*\.inc"', source)
     assert "wn[k] = w32768(k * (16384 / M))" in source
-    assert not re.search(r"\b(sinf?|cosf?|sincosf?|__sinf|__cosf)\s*\(", re.sub(r"//[^\n]*", "", source))
+    for text in (source, shared):
+        assert not re.search(r"\b(sinf?|cosf?|sincosf?|__sinf|__cosf)\s*\(", re.sub(r"//[^\n]*", "", text))
     for n in LENGTHS:
         assert (n // 2 - 1) * (16384 // (n // 2)) < 16384
 
 
 # ---- 2: ISA budget and inventory -------------------------------------------------------------------------------
-def _occupancy(vgprs):
-    """waves per SIMD that the vector registers allow: 512 registers in granules of 8"""
-    return 512 // (-(-vgprs // 8) * 8)
-
-
 @pytest.fixture(scope="module")
 def isa(tmp_path_factory):
     """{M: assembly of smfft_stft_<M>.o as the Makefile compiles it}"""
     if not os.path.exists(ac.HIPCC):
         pytest.skip("hipcc not installed")
-    tmp = tmp_path_factory.mktemp("stft_isa")
-
-    def compile_one(args):
-        m, marked = args
-        flags = ["-I" + CSRC] + ac.makefile_flags("STFT", m) + [f"-DSMFFT_STFT_N={m}"] + (["-DSMFFT_STFT_NT_LOAD=1"] if marked else [])
-        return ac.device_asm(os.path.join(CSRC, "smfft_stft.hip"), flags, tmp / f"smfft_stft_{m}_{int(marked)}.s")
-    jobs = [(m, marked) for marked in (False, True) for m in SIZES]
-    with concurrent.futures.ThreadPoolExecutor(5) as pool:
-        texts = list(pool.map(compile_one, jobs))
     # what ships, and the same source with the sample loads marked non-temporal, which tells them from the window's and the twiddles'
-    return dict(zip(SIZES, texts[:5])), dict(zip(SIZES, texts[5:]))
+    return (ac.addon_isa("smfft_stft", "STFT", SIZES, tmp_path_factory.mktemp("stft_isa")),
+            ac.addon_isa("smfft_stft", "STFT", SIZES, tmp_path_factory.mktemp("stft_isa_marked"), extra=["-DSMFFT_STFT_NT_LOAD=1"]))
 
 
 def test_isa_budget_of_what_ships(isa):
@@ -217,9 +206,9 @@ def test_isa_budget_of_what_ships(isa):
             assert ac.descriptor_field(descs, name, "private_segment_fixed_size") == 0, name
             v, lds = ac.descriptor_field(descs, name, "next_free_vgpr"), ac.descriptor_field(descs, name, "group_segment_fixed_size")
             label = "istft_kernel" if family == "istft" else f"stft_kernel, kind {int(power)}"
-            print(f"M={m}: {label}: {v} VGPRs ({_occupancy(v)} waves per SIMD), {lds} B of LDS, 0 B of scratch")
+            print(f"M={m}: {label}: {v} VGPRs ({ac.occupancy(v)} waves per SIMD), {lds} B of LDS, 0 B of scratch")
             assert lds == LDS_BUDGET and 2 * lds <= ac.LDS_PER_CU, (name, lds)
-            assert v <= 256 and _occupancy(v) >= 2, (name, v)
+            assert v <= 256 and ac.occupancy(v) >= 2, (name, v)
             loads = [i for i, line in enumerate(body) if line.startswith("global_load")]
             stores = [i for i, line in enumerate(body) if line.startswith("global_store")]
             rows = [i for i in loads if re.search(r"\bnt\b", body[i])]             # the inverse's bins: non-temporal; the rest: plain
@@ -245,10 +234,7 @@ def test_library_ships_fifteen_kernels_and_the_inventory_names_them(stft_lib):
 def test_isa_identity_compares_the_library():
     """tools/isa_identity.py compiles the five objects with the Makefile's flags and -I., like the other add-ons' (the tool itself
     needs the history of a git checkout and minutes of compiling: it is run by hand, DESIGN.md section 25 has its verdict)"""
-    import isa_identity
-    assert ("smfft_stft", "STFT", SIZES, True) in isa_identity.ADDONS
-    names = [u[0] for u in isa_identity.units(ROOT)]
-    assert all(f"smfft_stft_{m}" in names for m in SIZES) and len(names) == len(set(names))
+    ac.check_isa_identity_lists("smfft_stft", "STFT", SIZES)
     assert all("-ffp-contract=on" in ac.makefile_flags("STFT", m) for m in SIZES)
 
 
@@ -284,8 +270,8 @@ def test_python_mirror_matches_header(stft_lib):
 
 
 def test_library_exports_exactly_the_eight_symbols(stft_lib):
-    nm = subprocess.run(["nm", "-D", "--defined-only", stft_lib], capture_output=True, text=True, check=True).stdout
-    assert sorted(re.findall(r" T (smfft_\w+)$", nm, re.M)) == sorted(NAMES) and len(NAMES) == 8
+    ac.check_exports(stft_lib, NAMES)
+    assert len(NAMES) == 8
 
 
 # ---- 4: rejections -------------------------------------------------------------------------------------------------
@@ -360,18 +346,12 @@ def test_python_wrappers_refuse_before_a_device(stft_lib):
     """in a process where no GPU is visible: the pointer forms turn the library's -1 into a RuntimeError, the tensor forms raise
     ValueError or TypeError themselves -- float64, wrong ranks, non-contiguous tensors, windows of another length, tensors on the
     host -- a zero count is served, and overlap_add / hann / frames are what they say"""
-    code = r"""
+    code = ac.REFUSED + r"""
 import sys
 sys.path.insert(0, sys.argv[1])
 import numpy as np
 from smfft_amd import stft
 IN, OUT, WIN = 1 << 30, 1 << 40, 1 << 20
-def refused(exc, f, *a, **k):
-    try:
-        f(*a, **k)
-    except exc:
-        return
-    raise SystemExit(f"{f.__name__}{a}{k} was not refused with {exc.__name__}")
 for n in (256, 500, 16384, 0):
     refused(RuntimeError, stft.launch_ptr, IN, OUT, WIN, n, 2, 5, 128, 4096)
     refused(RuntimeError, stft.launch_ptr, IN, OUT, WIN, n, 2, 5, 128, 4096, power=True, grid=3)
@@ -438,7 +418,4 @@ print("ok")
 
 
 def test_import_does_not_load_the_library():
-    code = ("import sys; sys.path.insert(0, sys.argv[1]); import smfft_amd, smfft_amd.stft as l; assert l._lib is None; "
-            "maps = open('/proc/self/maps').read(); assert 'libsmfft_stft' not in maps; print('ok')")
-    p = subprocess.run([sys.executable, "-c", code, ROOT], capture_output=True, text=True, timeout=120)
-    assert p.returncode == 0 and "ok" in p.stdout, p.stdout + p.stderr
+    ac.check_import_does_not_load("stft", "smfft_stft")

@@ -26,7 +26,8 @@ import numpy as np
 import pytest
 
 from tests import guarded_region
-from tests.fir_gpu_harness import GUARD, ROW_MAX, ROW_REL_L2
+from tests import rows_gpu_harness as rh
+from tests.fir_gpu_harness import ROW_MAX, ROW_REL_L2
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
 import stft_model as mm  # noqa: E402
@@ -36,7 +37,7 @@ pytestmark = pytest.mark.gpu
 LENGTHS = [512, 1024, 2048, 4096, 8192]
 KINDS = ["complex", "power", "inverse"]
 FACTOR = {"complex": 1.0, "power": 2.0, "inverse": 1.0}
-WORST = {}                  # kind -> [relL2, max / max]: the worst figures measured in this run
+WORST = rh.Worst()      # kind -> [relL2, max / max]: the worst figures measured in this run
 E = 4                       # bytes per float
 C, F = 3, 7                 # streams and frames per stream of the small shapes
 
@@ -55,17 +56,9 @@ def st():
     return stft
 
 
-def _rand(rng, shape):
-    return rng.standard_normal(shape).astype(np.float32)
-
-
 def _spectra(rng, shape):
     """rows of bins, with an imaginary part on bins 0 and M as well: the inverse ignores it"""
     return (rng.standard_normal(shape) + 1j * rng.standard_normal(shape)).astype(np.complex64)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def _hann(n):
@@ -103,37 +96,10 @@ def _check_rows(got, want, kind, what, factor=None):
     d = got.astype(want.dtype) - want
     l2 = np.linalg.norm(d, axis=1) / np.maximum(np.linalg.norm(want, axis=1), 1e-300)
     mx = np.max(np.abs(d), axis=1) / np.maximum(np.max(np.abs(want), axis=1), 1e-300)
-    worst = WORST.setdefault(kind, [0.0, 0.0])
-    worst[0], worst[1] = max(worst[0], float(l2.max())), max(worst[1], float(mx.max()))
+    worst = WORST.record(kind, l2, mx)
     print(f"{what}: worst row relL2 = {l2.max():.3e}, max |d| / max |want| = {mx.max():.3e}  ({kind} so far: {worst[0]:.3e}, {worst[1]:.3e})")
     assert l2.max() <= factor * ROW_REL_L2 and mx.max() <= factor * ROW_MAX, \
         f"{what}: row {int(np.argmax(l2))} relL2 = {l2.max():.3e}, row {int(np.argmax(mx))} max = {mx.max():.3e}"
-
-
-def _guarded(sm, count):
-    """a device buffer of [GUARD | count | GUARD] float32: 0x5A, 0xFF, 0x5A; returns (buffer, the payload's address)"""
-    buf = sm.DeviceBuffer((count + 2 * GUARD) * E)
-    assert sm.lib.smfft_memset(buf.ptr, 0x5A, buf.nbytes) == 0
-    if count:
-        assert sm.lib.smfft_memset(buf.ptr + E * GUARD, 0xFF, E * count) == 0
-    return buf, buf.ptr + E * GUARD
-
-
-def _collect(buf, count, finite=True):
-    raw = buf.to_host(np.uint8, ((count + 2 * GUARD) * E,))
-    assert np.all(raw[:E * GUARD] == 0x5A), "the kernel wrote in front of its output"
-    assert np.all(raw[E * (GUARD + count):] == 0x5A), "the kernel wrote past its output"
-    out = raw[E * GUARD:E * (GUARD + count)].view(np.float32).copy()
-    if finite:
-        assert np.all(np.isfinite(out)), "outputs left unwritten"
-    return out
-
-
-def _upload(sm, a):
-    a = np.ascontiguousarray(a)
-    buf = sm.DeviceBuffer(a.nbytes)
-    assert buf.nbytes == a.nbytes and sm.lib.smfft_memcpy_h2d(buf.ptr, a.ctypes.data, a.nbytes) == 0
-    return buf
 
 
 def run_stft(sm, st, flat, w, n, streams, frames, hop, stride, kind, grid=None, finite=True, launch=None):
@@ -146,8 +112,8 @@ def run_stft(sm, st, flat, w, n, streams, frames, hop, stride, kind, grid=None, 
     assert w is None or (w.dtype == np.float32 and w.shape == (n,))
     bins = n // 2 + 1
     floats = streams * frames * bins * (2 if kind == "complex" else 1)
-    dout, pout = _guarded(sm, floats)
-    din, dw = _upload(sm, flat), None if w is None else _upload(sm, w)
+    dout, pout = rh.guarded(sm, floats, E)
+    din, dw = rh.upload(sm, flat), None if w is None else rh.upload(sm, w)
     try:
         pw = None if dw is None else dw.ptr
         if launch is None:
@@ -155,7 +121,7 @@ def run_stft(sm, st, flat, w, n, streams, frames, hop, stride, kind, grid=None, 
         else:
             launch(din.ptr, pout, pw)
         assert sm.lib.smfft_synchronize() == 0
-        out = _collect(dout, floats, finite)
+        out = rh.collect(dout, floats, np.float32, finite=finite)
         return (out.view(np.complex64) if kind == "complex" else out).reshape(streams * frames, bins)
     finally:
         for buf in (din, dout, dw):
@@ -168,8 +134,8 @@ def run_istft(sm, st, X, w, n, grid=None, finite=True, launch=None):
     X = np.ascontiguousarray(X)
     assert X.dtype == np.complex64 and X.ndim == 2 and X.shape[1] == n // 2 + 1
     batch = X.shape[0]
-    dout, pout = _guarded(sm, batch * n)
-    din, dw = _upload(sm, X), None if w is None else _upload(sm, w)
+    dout, pout = rh.guarded(sm, batch * n, E)
+    din, dw = rh.upload(sm, X), None if w is None else rh.upload(sm, w)
     try:
         pw = None if dw is None else dw.ptr
         if launch is None:
@@ -177,7 +143,7 @@ def run_istft(sm, st, X, w, n, grid=None, finite=True, launch=None):
         else:
             launch(din.ptr, pout, pw)
         assert sm.lib.smfft_synchronize() == 0
-        return _collect(dout, batch * n, finite).reshape(batch, n)
+        return rh.collect(dout, batch * n, np.float32, finite=finite).reshape(batch, n)
     finally:
         for buf in (din, dout, dw):
             if buf is not None:
@@ -190,7 +156,7 @@ def _case(rng, kind, n):
         X = _spectra(rng, (C * F, n // 2 + 1))
         return X, X
     hop, stride, total = _geometry(n)
-    flat = _rand(rng, (total,))
+    flat = rh.rand(rng, (total,))
     return flat, _rows_of(flat, n, C, F, hop, stride)
 
 
@@ -225,13 +191,13 @@ def test_frames_from_the_signal_are_the_copied_rows(sm, st, n):
     w = _ramp(n)
     for hop, pad in ((n // 4, 0), (n // 4 + 1, 13), (37, 5), (n, 12)):
         stride = (F - 1) * hop + n + pad
-        flat = _rand(rng, ((C - 1) * stride + (F - 1) * hop + n,))
+        flat = rh.rand(rng, ((C - 1) * stride + (F - 1) * hop + n,))
         rows = _rows_of(flat, n, C, F, hop, stride)
         for kind in ("complex", "power"):
             base = run_stft(sm, st, rows.reshape(-1), w, n, C * F, 1, n, n, kind)
             _check_rows(base, _want(kind, rows, w), kind, f"n={n} {kind} copied-out rows, hop {hop}")
             got = run_stft(sm, st, flat, w, n, C, F, hop, stride, kind)
-            assert np.array_equal(_bits(got), _bits(base)), (n, hop, stride, kind)
+            assert np.array_equal(rh.bits(got), rh.bits(base)), (n, hop, stride, kind)
 
 
 # ---- 3: exact probes ----------------------------------------------------------------------------------------------------------------
@@ -251,7 +217,7 @@ def test_probe_impulses(sm, st, n):
         want = np.stack([wj[j] * np.exp(-2j * np.pi * j * k / n) for j in js])
         got = run_stft(sm, st, x.reshape(-1), w, n, len(js), 1, n, n, "complex")
         _check_rows(got, want, "complex", f"n={n} impulses at {js}, window {name}")
-        assert not _bits(got.imag[:, [0, M]]).any(), "the imaginary parts of X[0] and X[M] are not +0"
+        assert not rh.bits(got.imag[:, [0, M]]).any(), "the imaginary parts of X[0] and X[M] are not +0"
         got = run_stft(sm, st, x.reshape(-1), w, n, len(js), 1, n, n, "power")
         _check_rows(got, np.abs(want) ** 2, "power", f"n={n} power of impulses at {js}, window {name}")
         ks = [0, 1, M - 1, M]
@@ -263,10 +229,10 @@ def test_probe_impulses(sm, st, n):
         _check_rows(got, want, "inverse", f"n={n} single bins at {ks}, window {name}")
         X[0, 0] = 1 + 3j
         X[3, M] = 1 - 2j
-        assert np.array_equal(_bits(run_istft(sm, st, X, w, n)), _bits(got)), "an imaginary part on bin 0 or M shows"
+        assert np.array_equal(rh.bits(run_istft(sm, st, X, w, n)), rh.bits(got)), "an imaginary part on bin 0 or M shows"
     # Gaussian frames: the two real bins carry +0 as well
-    got = run_stft(sm, st, _rand(np.random.default_rng(n), (5 * n,)), _hann(n), n, 5, 1, n, n, "complex")
-    assert not _bits(got.imag[:, [0, M]]).any()
+    got = run_stft(sm, st, rh.rand(np.random.default_rng(n), (5 * n,)), _hann(n), n, 5, 1, n, n, "complex")
+    assert not rh.bits(got.imag[:, [0, M]]).any()
 
 
 # ---- 4: isolation -------------------------------------------------------------------------------------------------------------------
@@ -276,7 +242,7 @@ def test_probe_rows_are_isolated(sm, st, n):
     bits of the clean run, for both kinds; one NaN bin makes its row of the inverse NaN and no other"""
     hop, stride, total = _geometry(n)
     w = _hann(n)
-    flat = _rand(np.random.default_rng(30 + n), (total,))
+    flat = rh.rand(np.random.default_rng(30 + n), (total,))
     pos = 2 * hop + 5                                  # inside frames 0, 1, 2 of stream 1 (and, with n = 4 hop - 4, of frame 3 not)
     covering = [F + f for f in range(F) if f * hop <= pos < f * hop + n]
     assert covering == [F, F + 1, F + 2]
@@ -287,13 +253,13 @@ def test_probe_rows_are_isolated(sm, st, n):
         clean = run_stft(sm, st, flat, w, n, C, F, hop, stride, kind)
         got = run_stft(sm, st, bad, w, n, C, F, hop, stride, kind, finite=False)
         assert np.isnan(got[covering]).all(), (n, kind)
-        assert np.array_equal(_bits(got[others]), _bits(clean[others])), (n, kind)
+        assert np.array_equal(rh.bits(got[others]), rh.bits(clean[others])), (n, kind)
     X = _spectra(np.random.default_rng(31 + n), (C * F, n // 2 + 1))
     clean = run_istft(sm, st, X, w, n)
     X[9, n // 4] = np.nan
     got = run_istft(sm, st, X, w, n, finite=False)
     # (the window's first sample is zero times NaN: NaN as well)
-    assert np.isnan(got[9]).all() and np.array_equal(_bits(np.delete(got, 9, 0)), _bits(np.delete(clean, 9, 0))), n
+    assert np.isnan(got[9]).all() and np.array_equal(rh.bits(np.delete(got, 9, 0)), rh.bits(np.delete(clean, 9, 0))), n
 
 
 @pytest.mark.parametrize("n", LENGTHS)
@@ -312,9 +278,9 @@ def test_position_and_grid_are_invisible(sm, st, n):
                 alone = run_istft(sm, st, rows[r:r + 1], w, n)
             else:
                 alone = run_stft(sm, st, rows[r], w, n, 1, 1, 1, 1, kind)
-            assert np.array_equal(_bits(alone[0]), _bits(base[r])), (n, kind, r)
+            assert np.array_equal(rh.bits(alone[0]), rh.bits(base[r])), (n, kind, r)
         for grid in (1, 3):
-            assert np.array_equal(_bits(_run(sm, st, kind, n, data, w, grid=grid)), _bits(base)), (n, kind, grid)
+            assert np.array_equal(rh.bits(_run(sm, st, kind, n, data, w, grid=grid)), rh.bits(base)), (n, kind, grid)
 
 
 # ---- 5: the grid-stride loop ----------------------------------------------------------------------------------------------------------
@@ -329,12 +295,12 @@ def test_grid_stride_loop(sm, st, kind):
         got, base, want = run_istft(sm, st, X, w, n, grid=2), run_istft(sm, st, X, w, n), _want(kind, X, w)
     else:
         hop = n // 4 + 1
-        flat = _rand(rng, ((frames - 1) * hop + n,))
+        flat = rh.rand(rng, ((frames - 1) * hop + n,))
         got = run_stft(sm, st, flat, w, n, 1, frames, hop, flat.size, kind, grid=2)
         base = run_stft(sm, st, flat, w, n, 1, frames, hop, flat.size, kind)
         want = _want(kind, _rows_of(flat, n, 1, frames, hop, flat.size), w)
     _check_rows(got, want, kind, f"grid-stride n={n} frames={frames} {kind}")
-    assert np.array_equal(_bits(got), _bits(base))
+    assert np.array_equal(rh.bits(got), rh.bits(base))
 
 
 # ---- 6: the power ---------------------------------------------------------------------------------------------------------------------
@@ -343,7 +309,7 @@ def test_power_is_the_square_of_the_complex_kind(sm, st, n):
     """kind 1 is re * re + im * im of kind 0's values: within 2 ulp of that sum computed in fp32 from the kind-0 output (one ulp for
     the fused multiply-add of the kernel against the two roundings here, one to spare)"""
     hop, stride, total = _geometry(n)
-    flat = _rand(np.random.default_rng(55 + n), (total,))
+    flat = rh.rand(np.random.default_rng(55 + n), (total,))
     w = _hann(n)
     X = run_stft(sm, st, flat, w, n, C, F, hop, stride, "complex")
     P = run_stft(sm, st, flat, w, n, C, F, hop, stride, "power")
@@ -362,7 +328,7 @@ def test_round_trip(sm, st, n):
     (The sum is NumPy's here; smfft_amd.stft.overlap_add / istft are held to torch in test_tensors_on_the_device.)"""
     streams, frames, hop = 2, 12, n // 4
     L = (frames - 1) * hop + n
-    s = _rand(np.random.default_rng(25 + n), (streams, L))
+    s = rh.rand(np.random.default_rng(25 + n), (streams, L))
     w = _hann(n)
     X = run_stft(sm, st, s.reshape(-1), w, n, streams, frames, hop, L, "complex")
     y = run_istft(sm, st, X, w, n).reshape(streams, frames, n)
@@ -388,7 +354,7 @@ def test_bounds(sm, st, n, frames):
             base = run_istft(sm, st, x, w, n)
             rows, out_bytes, in_off = x, frames * n * E, 0
         else:
-            x = _rand(rng, ((frames - 1) * hop + n,))
+            x = rh.rand(rng, ((frames - 1) * hop + n,))
             base = run_stft(sm, st, x, w, n, 1, frames, hop, x.size, kind)
             rows, out_bytes, in_off = _rows_of(x, n, 1, frames, hop, x.size), base.nbytes, 4
         _check_rows(base, _want(kind, rows, w), kind, f"n={n} frames={frames} {kind}")
@@ -405,7 +371,7 @@ def test_bounds(sm, st, n, frames):
             rw.outside_unchanged(whole=True)
             got = rout.outside_unchanged(whole=False).view(np.float32)
             assert np.all(np.isfinite(got)), "outputs left unwritten"
-            assert np.array_equal(_bits(got), _bits(base).reshape(-1)), (n, frames, kind)
+            assert np.array_equal(rh.bits(got), rh.bits(base).reshape(-1)), (n, frames, kind)
         finally:
             for r in (rin, rout, rw):
                 r.buf.free()
@@ -465,7 +431,7 @@ def test_benchmark_forms_add_to_the_timer(sm, st):
                 status, ms = st.stft_benchmark(pin, pout, pw, n, C, F, hop, stride, power=kind == "power")
             assert status == 0 and ms > 0.0
         for form in (c_form, mirror):
-            assert np.array_equal(_bits(_run(sm, st, kind, n, data, w, launch=form)), _bits(base)), (kind, form.__name__)
+            assert np.array_equal(rh.bits(_run(sm, st, kind, n, data, w, launch=form)), rh.bits(base)), (kind, form.__name__)
 
 
 _TENSOR_SCRIPT = r"""
