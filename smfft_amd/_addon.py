@@ -1,4 +1,4 @@
-"""The loader that the ctypes mirrors of the add-on libraries share (large, large_real, large_fir, pfb, pfb_real, large_pfb, pfb_spec, fir_real, fir_detect, bluestein, czt, rowconv, rowconv_real, dct, hilbert, mdct, stft, welch; the polyphase filter banks share more: _pfb_bank.py, the FIR filter banks: _fir_bank.py, the half-length real-row libraries dct, hilbert, mdct, stft and welch: _rows.py): each library is loaded on first
+"""The loader that the ctypes mirrors of the add-on libraries share (large, large_real, large_fir, pfb, pfb_real, large_pfb, pfb_spec, fir_real, fir_detect, bluestein, czt, rowconv, rowconv_real, dct, hilbert, mdct, stft, welch, bands; the polyphase filter banks share more: _pfb_bank.py, the FIR filter banks: _fir_bank.py, the half-length real-row libraries dct, hilbert, mdct, stft, welch and bands: _rows.py): each library is loaded on first
 use, so that `import smfft_amd` behaves the same whether it was built or not, and a missing one raises on the first call."""
 import ctypes
 import os

@@ -1,4 +1,4 @@
-"""What the ctypes mirrors of the half-length real-row libraries share beside the loader of _addon.py (dct, hilbert, mdct, stft, welch): the
+"""What the ctypes mirrors of the half-length real-row libraries share beside the loader of _addon.py (dct, hilbert, mdct, stft, welch, bands): the
 check of a tensor argument and the host round trip of the array forms.  Private: the mirrors' public names stay their own."""
 import numpy as np
 

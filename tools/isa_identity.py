@@ -5,8 +5,8 @@ Compiles, on a checkout of BASE (git archive into a temporary directory) and on 
   smfft_amd/csrc/smfft_inst.hip   both objects (SMFFT_INST_PART = 1, 2 with tools/inst_flags.py) of all 8 lengths
   smfft_amd/csrc/smfft_fir.hip    the main library's FIR object (all five lengths in one unit, the main library's flags)
   smfft_amd/csrc/smfft_large.hip, smfft_large_real.hip, smfft_large_fir.hip, smfft_pfb.hip, smfft_pfb_real.hip, smfft_large_pfb.hip, smfft_pfb_spec.hip,
-  smfft_fir_real.hip, smfft_fir_detect.hip, smfft_bluestein.hip, smfft_czt.hip, smfft_rowconv.hip, smfft_rowconv_real.hip, smfft_dct.hip, smfft_hilbert.hip, smfft_mdct.hip, smfft_stft.hip, smfft_welch.hip   the per-length objects of the eighteen add-on libraries, each with its <PREFIX>_FLAGS_<N> of the Makefile
-                                  (and the -I. of the sixteen that include headers of that directory), where BASE has the file
+  smfft_fir_real.hip, smfft_fir_detect.hip, smfft_bluestein.hip, smfft_czt.hip, smfft_rowconv.hip, smfft_rowconv_real.hip, smfft_dct.hip, smfft_hilbert.hip, smfft_mdct.hip, smfft_stft.hip, smfft_welch.hip, smfft_bands.hip   the per-length objects of the nineteen add-on libraries, each with its <PREFIX>_FLAGS_<N> of the Makefile
+                                  (and the -I. of the seventeen that include headers of that directory), where BASE has the file
   examples/*.hip                  the files BASE has
 to device assembly (hipcc -S --cuda-device-only) and compares every kernel BASE has, text of its body and its .amdhsa descriptor,
 with the basic-block labels (.LBB<f>_<n>) and the function-local symbols renumbered in order of appearance.  A kernel whose text differs
@@ -38,7 +38,8 @@ ADDONS = (("smfft_large", "LARGE", (8192, 16384), False), ("smfft_large_real", "
           ("smfft_czt", "CZT", (256, 512, 1024, 2048, 4096), True), ("smfft_rowconv", "ROWCONV", (256, 512, 1024, 2048, 4096), True),
           ("smfft_rowconv_real", "ROWCONV_REAL", (256, 512, 1024, 2048, 4096), True), ("smfft_dct", "DCT", (256, 512, 1024, 2048, 4096), True),
           ("smfft_hilbert", "HILBERT", (256, 512, 1024, 2048, 4096), True), ("smfft_mdct", "MDCT", (256, 512, 1024, 2048, 4096), True),
-          ("smfft_stft", "STFT", (256, 512, 1024, 2048, 4096), True), ("smfft_welch", "WELCH", (256, 512, 1024, 2048, 4096), True))
+          ("smfft_stft", "STFT", (256, 512, 1024, 2048, 4096), True), ("smfft_welch", "WELCH", (256, 512, 1024, 2048, 4096), True),
+          ("smfft_bands", "BANDS", (256, 512, 1024, 2048, 4096), True))
 
 
 def addon_flags(prefix, n):
